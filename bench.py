@@ -11,8 +11,10 @@ The timed region drives the product's clip pipeline, vps_amd.clip_shard.ClipShar
 clip of N*K frames is sharded contiguously over the N ranks (K frames each: per-GPU work fixed as N grows -> "weak"), every
 shard boundary costs one point-to-point RCCL send/recv of the 134 MB gathered pre-neck feature, and the sequential tracker
 replay on rank 0 plus the gather of all per-frame results are INSIDE the timed region. At N=1 it is the plain sequential
-path. After the timed region (untimed extras, rank 0): an instrumented frame for the roofline numbers, micro-timings of the
-HBM-bound kernels, the fixed 30-frame clip of config 4 (strong scaling, field `clip30`), and the CPU baseline.
+path. A plain run sets up, warms up, times the K steps, writes the outputs of the last timed frame (`--dump-outputs DIR`) and
+prints the headline line. `--full` adds, after the timed region (untimed extras, rank 0): an instrumented frame for the roofline
+numbers, micro-timings of the HBM-bound kernels, the fixed 30-frame clip of config 4 (strong scaling, field `clip30`), the other
+fp32-grade arithmetic, the per-call loop, the PNG-fed clip, the multi-GPU cost model and the CPU baseline.
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -196,6 +198,36 @@ def hbm_kernels(dev):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out, d):
+    """`--dump-outputs DIR`: the arrays the caller of the timed path received for the last timed frame, one DIR/<name>.npy each, for
+    comparing two builds output for output. Float arrays are written as float32, integer ones as float32 (the uint8 maps) or float64
+    (the int64 class indices, labels and track ids), so that every value stays exact. An array that would take the files past 64 MB in
+    all is replaced by a fixed sample of its flattened elements (seeded index set, sorted) under DIR/<name>.sample.npy, the indices
+    beside it."""
+    os.makedirs(d, exist_ok=True)
+    arrs = {}
+    for k, v in sorted(out.items()):
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        if not isinstance(v, np.ndarray) or v.dtype.kind not in 'biuf':
+            continue
+        arrs[k] = v.astype(np.float32 if v.dtype.itemsize <= (4 if v.dtype.kind == 'f' else 2) else np.float64)
+    left = DUMP_BUDGET_BYTES
+    for k, v in sorted(arrs.items(), key=lambda kv: kv[1].nbytes):          # small ones first: they are always written whole
+        if v.nbytes <= left:
+            np.save(os.path.join(d, k + '.npy'), v)
+            left -= v.nbytes
+            continue
+        n = max(1, min(v.size, left // (v.itemsize + 8) // 2))
+        idx = np.sort(np.random.default_rng(0).choice(v.size, n, replace=False))
+        np.save(os.path.join(d, k + '.sample.npy'), v.reshape(-1)[idx])
+        np.save(os.path.join(d, k + '.sample_index.npy'), idx.astype(np.float64))
+        left -= n * (v.itemsize + 8)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: re-run this command under torch.distributed.run, one rank per GPU over RCCL
     (the launcher the driver uses for N > 1: same environment contract), rendezvous on 127.0.0.1 at a free port. A box with fewer
@@ -224,8 +256,11 @@ def main():
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--seed', type=int, default=0)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the untimed extras (hbm kernel table, 30-frame clip)')
+    ap.add_argument('--full', action='store_true', help='after the timed region also run the untimed extras (instrumented frame / roofline, '
+                    'hbm kernel table, 30-frame clip, other arithmetic, per-call loop, PNG-fed clip, scaling model, CPU baseline)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write the outputs of the last timed frame as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the untimed extras (hbm kernel table, 30-frame clip)')
     ap.add_argument('--height', type=int, default=H)
     ap.add_argument('--width', type=int, default=W)
     ap.add_argument('--prec', default=DEFAULT_PREC, choices=['f32', 'bf16', 'bf16x3', 'bf16x6', 'f16x3'], help='arithmetic of the dense contractions')
@@ -233,11 +268,16 @@ def main():
                     help='detector (SURVEY 8(f) row 4): the headline metric is fusetrack; the variants are single-GPU only')
     ap.add_argument('--model-config', default=None, help='model config file (default configs/cityscapes/<variant>.py); BASELINE config 5: '
                     'configs/viper/fusetrack_r101.py --height 1088 --width 1920 --prec bf16')
-    ap.add_argument('--conv-table', default=None, help='write the per-layer-shape conv timing table of one frame here')
+    ap.add_argument('--conv-table', default=None, help='with --full: write the per-layer-shape conv timing table of one frame here')
     ap.add_argument('--no-prefetch', action='store_true', help='do not enqueue the next frame behind the current one (A/B of the clip pipelining)')
     ap.add_argument('--single-stream', action='store_true', help='run every frame on one stream (for kernel traces whose durations add up)')
     ap.add_argument('--png-workers', type=int, default=6, help='decode threads of the `from_png` leg (frames read from PNG files through vps_amd.pipeline.ClipFeeder)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.conv_table and not args.full:
+        ap.error('--conv-table is written by the instrumented frame of --full')
+    extras = args.full and not args.no_extras
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return self_launch(args.gpus)
@@ -323,15 +363,18 @@ def main():
     # ---- timed region: exactly K frames per rank --------------------------------------------------------------------------------
     t0 = time.perf_counter()
     ndet = 0
+    last = None                  # rank 0: what the caller of the timed path received for the last timed frame
     if use_runner:
         outs = runner.run(load_frame, args.steps * world, video_id=2)
         if rank == 0:
             assert len(outs) == args.steps * world
             ndet = sum(int(o['panoptic_cls_inds'].numel()) for o in outs)
+            last = outs[-1]
     else:
         for t in range(args.steps):
             out = plain_step(t, 2)
             ndet += int(out[2]['panoptic_cls_inds'].numel())
+        last = out[2]
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
@@ -343,10 +386,12 @@ def main():
         dt = float(tmax.item())
     total_frames = args.steps * world
     ws_timed_gb = round(model.workspace_bytes() / 1e9, 2) if hasattr(model, 'workspace_bytes') else None      # what the timed configuration holds
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(last, args.dump_outputs)
 
-    # ---- untimed: BASELINE config 4 as stated — the fixed 30-frame clip over N GPUs (strong scaling) ----------------------------
+    # ---- untimed (--full): BASELINE config 4 as stated — the fixed 30-frame clip over N GPUs (strong scaling) ---------------------
     clip30 = None
-    if use_runner and not args.no_extras:
+    if use_runner and extras:
         reset()
         torch.cuda.synchronize()
         if use_dist:
@@ -368,9 +413,9 @@ def main():
                           note='one 30-frame synthetic clip over %d GPU(s): %d feature hand-off(s), tracker replay on rank 0 and result gather inside' % (world, world - 1),
                           id_checksum=int(sum(sig)))
 
-    # ---- untimed: the same pipeline in the other fp32-grade arithmetic (bf16x6: 6 bf16 MFMAs per product), for comparison ----------
+    # ---- untimed (--full): the same pipeline in the other fp32-grade arithmetic (bf16x6: 6 bf16 MFMAs per product), for comparison ---
     other = None
-    if use_runner and not args.no_extras and world == 1 and args.prec == 'f16x3' and (Hh, Ww) == (H, W):
+    if use_runner and extras and world == 1 and args.prec == 'f16x3' and (Hh, Ww) == (H, W):
         old = nhwc.DEFAULT_PREC
         nhwc.DEFAULT_PREC = hip.PREC_BF16X6
         try:
@@ -392,13 +437,13 @@ def main():
         del m2, r2
         torch.cuda.empty_cache()
 
-    # ---- untimed: what the UNMODIFIED tools/test_vpq.py:41-63 loop gets after the import switch of INTEGRATION.md Level 1 (build_detector,
+    # ---- untimed (--full): what the UNMODIFIED tools/test_vpq.py:41-63 loop gets after the import switch of INTEGRATION.md Level 1 (build_detector,
     # build_dataloader and MMDataParallel from vps_amd): one model(...) call per frame over a data loader, the two maps and the instance
     # vectors fetched to the host after every frame. The loader stand-in yields the reference's test batches (img / img_meta in a
     # cpu_only DataContainer / ref_img, ref_img a tensor of its own like cityscapes_vps.py:137-148 loads it); vps_amd.LookaheadLoader
     # keeps two batches ahead and announces them to the detector (round 6). `no_lookahead`: the same loop over the bare loader (round 5).
     plain = None
-    if rank == 0 and not args.no_extras and args.variant == 'fusetrack':
+    if rank == 0 and extras and args.variant == 'fusetrack':
         import vps_amd as _va
         nfr = 20
 
@@ -443,10 +488,10 @@ def main():
                           'uint8 maps and the instance vectors after every frame; no_lookahead: the same loop over the bare loader')
         reset()
 
-    # ---- untimed: the same clip pipeline fed from PNG FILES: vps_amd.pipeline.ClipFeeder decodes with a pool of host
+    # ---- untimed (--full): the same clip pipeline fed from PNG FILES: vps_amd.pipeline.ClipFeeder decodes with a pool of host
     # threads ahead of the detector, uploads the uint8 frame through pinned memory and normalises / pads on the device -----------------
     from_png = None
-    if rank == 0 and not args.no_extras and use_runner and world == 1:
+    if rank == 0 and extras and use_runner and world == 1:
         import shutil
         import tempfile
         from PIL import Image
@@ -494,10 +539,10 @@ def main():
             shutil.rmtree(tmpd, ignore_errors=True)
         reset()
 
-    # ---- untimed: inputs of the multi-GPU cost model (vps_amd.clip_shard.predict_clip_time) measured on this GPU, and its prediction for
+    # ---- untimed (--full): inputs of the multi-GPU cost model (vps_amd.clip_shard.predict_clip_time) measured on this GPU, and its prediction for
     # 2 / 4 / 8 GPUs - no RCCL run exists from this build (one GPU per box), so the first real one has something to be judged against
     scaling_model = None
-    if rank == 0 and not args.no_extras and use_runner and world == 1:
+    if rank == 0 and extras and use_runner and world == 1:
         from vps_amd.clip_shard import predict_clip_time
 
         def timed(fn, n):
@@ -534,9 +579,9 @@ def main():
                              note='critical-path model of ClipShardRunner (vps_amd/clip_shard.py:predict_clip_time), NOT a measurement: no multi-GPU run exists '
                                   'from this build. transfer time assumes ~48 GB/s for one point-to-point stream over one xGMI link')
 
-    # ---- instrumented extra frame (outside the timed region): per-stage and per-conv-launch HIP events, ONE stream ---------------
+    # ---- instrumented extra frame (--full, outside the timed region): per-stage and per-conv-launch HIP events, ONE stream --------
     roof, stages, hbm = None, None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         reset()
         plain_step(0, 4); plain_step(1, 4)
         # INSTR_FRAMES consecutive instrumented frames; every launch (and stage) is reported with the MEDIAN of its durations over
@@ -618,7 +663,7 @@ def main():
         roof['instrumented_frames'] = dict(conv_launches=len(runs), other_launches=len(lib_runs), stages=len(st_runs))   # per-launch medians over this many single-stream frames
         roof['in_frame_launch_us'] = {k: v for k, v in sorted(in_frame.items())}
         roof['in_frame_non_conv_ms'] = round(sum(sum(v) for v in in_frame.values()) * 1e-3, 3)
-        if not args.no_extras and (Hh, Ww) == (H, W):
+        if extras and (Hh, Ww) == (H, W):
             hbm = hbm_kernels(dev)
             # the same kernels INSIDE the frame (real operands, neighbours in the caches): achieved GB/s from the in-frame duration
             csym = 'vps_correlation_f16' if 'vps_correlation_f16' in in_frame else 'vps_correlation'       # f16x3 mode: split fp16 on MFMA where an instance exists
@@ -657,12 +702,14 @@ def main():
                                       '(FlowNetC-S-S chain | ResNet + FPN + gather | FlowNetSD; ring of three output slots); %d frame(s) announced: frame t+1 at the start of call t '
                                       'if not in flight, frame t+2 behind neck(t)' % (getattr(model, 'pre_streams', 1), DetectorBackend.prefetch_depth)) if (use_runner and not args.no_prefetch and not args.single_stream) else 'two HIP streams per frame' if not args.single_stream else 'one stream',
                        'workspace_GB': ws_timed_gb,
-                       'workspace_GB_after_the_untimed_extras': round(model.workspace_bytes() / 1e9, 2),       # + the one-stream instrumented frame, the per-call loop
                        'timed_region': 'inputs resident in HBM; excludes the H2D of the two 25 MB frames and the D2H of the two uint8 maps that '
                                        'tools/test_vpq.py:46-56 pays (~0.4 ms per frame over PCIe 5 x16 when not overlapped)'},
-            'roofline': roof, 'stage_ms': stages,
-            'stage_ms_note': 'median of 3 instrumented extra frames on ONE stream; the timed frames overlap the semantic head with the detection heads on two streams and the next frame\'s FlowNet2 + backbone + FPN on a third',
         }
+        if args.full:
+            line['config']['workspace_GB_after_the_untimed_extras'] = round(model.workspace_bytes() / 1e9, 2)     # + the one-stream instrumented frame, the per-call loop
+            line['roofline'], line['stage_ms'] = roof, stages
+            line['stage_ms_note'] = ('median of 3 instrumented extra frames on ONE stream; the timed frames overlap the semantic head with the detection heads on '
+                                     'two streams and the next frame\'s FlowNet2 + backbone + FPN on a third')
         if os.environ.get('VPS_S2_HALO', '1')[0] == '0':
             line['config']['experimental'] = 'VPS_S2_HALO=0: the phase-split stride-2 halo kernel switched off (A/B run, not the default configuration)'
         if plain is not None:
@@ -681,7 +728,7 @@ def main():
             line['clip30'] = clip30
         if other is not None:
             line['other_arithmetic'] = other
-        if not args.no_cpu_baseline and world == 1:          # the CPU leg is reported at N = 1 only (it takes about a minute of host time)
+        if args.full and not args.no_cpu_baseline and world == 1:          # the CPU leg is reported at N = 1 only (it takes about a minute of host time)
             line['cpu_baseline'] = cpu_baseline(args.seed)
     if use_dist:
         dist.barrier()

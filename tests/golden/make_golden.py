@@ -149,8 +149,10 @@ def main(variant='fusetrack', H=H, W=W, NFRAMES=NFRAMES, out_name=None, full=Fal
     out['map_stride'] = np.int64(map_stride)
     out['state_dict_manifest'] = np.frombuffer(manifest.encode(), dtype=np.uint8)
     path = os.path.join(HERE, out_name or '%s_clip.npz' % variant)
-    np.savez_compressed(path, **out)
-    print('wrote', path, os.path.getsize(path) / 1e6, 'MB')
+    sys.path.insert(0, os.path.dirname(HERE))
+    import golden_npz                                 # split into parts under the 1 MiB limit of a committed file
+    for f in golden_npz.save(path, out):
+        print('wrote', f, os.path.getsize(f) / 1e6, 'MB')
 
 
 if __name__ == '__main__':

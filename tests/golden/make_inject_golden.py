@@ -11,7 +11,7 @@ replaced by the injected tensors — `extra_neck` returns `inject_cases.neck_fea
 `cls_score` / `bbox_pred`, `mask_head` the injected mask logits — and `ref.simple_test` itself runs, untouched, from
 `simple_test_bboxes` to the returned dicts.
 
-    python tests/golden/make_inject_golden.py        # needs /root/reference; writes tests/golden/inject_cases.npz (~2 MB)
+    python tests/golden/make_inject_golden.py        # needs the reference sources; writes tests/golden/inject_cases.part*.npz (~2 MB)
 
 Stored per case / frame: MaskROI outputs, the comprehensive track scores, ids, kept list, the returned per-instance vectors,
 the two maps at stride 4 plus their label histograms over the full frame (the random semantic logits make the maps
@@ -134,8 +134,9 @@ def main():
             print('%s frame %d: K=%d M=%d kept=%d ids=%s' % (case, t, cap['mask_roi'][2].numel(), M_before, cap['keep_inds'].numel(),
                                                             out[p + 'panoptic_det_obj_ids'][:10]), flush=True)
     path = os.path.join(HERE, 'inject_cases.npz')
-    np.savez_compressed(path, **out)
-    print('wrote', path, os.path.getsize(path) / 1e6, 'MB')
+    import golden_npz                                 # split into parts under the 1 MiB limit of a committed file
+    for f in golden_npz.save(path, out):
+        print('wrote', f, os.path.getsize(f) / 1e6, 'MB')
 
 
 if __name__ == '__main__':

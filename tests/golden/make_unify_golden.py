@@ -138,5 +138,37 @@ def main(dataset='cityscapes_vps'):
     print('wrote', path, os.path.getsize(path), 'bytes')
 
 
+
+def pq_average_viper():
+    """tests/golden/viper_pq_average.json: what the REAL tools/dataset/viper.py:64-90 (PQStat.pq_average, `if label == 11: continue`)
+    returns for the per-class statistics of tests/test_evaluate.py::test_pq_average_viper_variant_excludes_mobilebarrier (same seed)"""
+    import json
+    warnings.simplefilter('ignore')
+    load_reference_function('tools.dataset.viper', 23, 11)
+    ref_mod = sys.modules['tools.dataset.viper']
+    cats = {c: {'isthing': 1 if c >= 13 else 0} for c in range(23)}
+    rng = np.random.default_rng(3)
+    vals = {}
+    for c in (2, 5, 11, 13, 17, 22):
+        tp, fp, fn = int(rng.integers(1, 9)), int(rng.integers(0, 5)), int(rng.integers(0, 5))
+        iou = float(rng.uniform(0.5, 1.0)) * tp
+        vals[c] = (tp, fp, fn, iou)
+    rs = ref_mod.PQStat()
+    for c, (tp, fp, fn, iou) in vals.items():
+        rs[c].tp, rs[c].fp, rs[c].fn, rs[c].iou = tp, fp, fn, iou
+    ref, ref_per = rs.pq_average(cats, None)
+    rec = dict(stats={str(c): list(v) for c, v in vals.items()},
+               result=dict(pq=float(ref['pq']), sq=float(ref['sq']), rq=float(ref['rq']), n=int(ref['n'])),
+               per_class=sorted(int(c) for c in ref_per))
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'viper_pq_average.json')
+    with open(path, 'w') as f:
+        json.dump(rec, f, indent=1)
+        f.write('\n')
+    print('wrote', path)
+
+
 if __name__ == '__main__':
-    main(sys.argv[1] if len(sys.argv) > 1 else 'cityscapes_vps')
+    if sys.argv[1:] == ['viper_pq_average']:
+        pq_average_viper()
+    else:
+        main(sys.argv[1] if len(sys.argv) > 1 else 'cityscapes_vps')

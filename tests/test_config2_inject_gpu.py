@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_npz
 import inject_cases as IC
 import vps_amd
 from inject_cases import CASES, H, W
@@ -43,7 +44,7 @@ def model(dev, request):
         nhwc.DEFAULT_PREC = old
     frames = [f.to(dev) for f in synth.synth_clip(H, W, 2, 0)]
     x = [l.to(dev) for l in IC.neck_features()]
-    return m, sd, frames, x, np.load(GOLD)
+    return m, sd, frames, x, golden_npz.load(GOLD)
 
 
 @pytest.mark.parametrize('case', list(CASES))

@@ -1,8 +1,5 @@
-"""BASELINE config 3 plumbing (VERDICT r4 missing #1, #3): `load_checkpoint` with mmcv's semantics, tools/run_config3.py on synthetic
-artefacts in the reference's file layout, and the REFERENCE'S OWN CALLER - tools/test_vpq.py:28-69 `single_gpu_test`, imported from
-/root/reference under the golden-vector import shims - driving the vps_amd detector through an MMDataParallel-style wrapper."""
-import ctypes
-import importlib.util
+"""BASELINE config 3 plumbing (VERDICT r4 missing #1, #3): `load_checkpoint` with mmcv's semantics and tools/run_config3.py on
+synthetic artefacts in the reference's file layout (the tools/test_vpq.py loop over the vps_amd loader and wrapper: tests/test_dataloader.py)."""
 import io
 import json
 import os
@@ -11,15 +8,13 @@ import sys
 from collections import OrderedDict
 from contextlib import redirect_stdout
 
-import numpy as np
 import pytest
 import torch
 
 import vps_amd
-from vps_amd import hip, synth
+from vps_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference'
 
 
 def _model():
@@ -88,98 +83,3 @@ def test_run_config3_dry_run_end_to_end(dev):
     j = json.loads(p.stdout.strip().splitlines()[-1])
     assert j['run']['frames'] == 16 and j['run']['decodes'] == 16 and j['run']['png_files'] == 4
     assert j['vpq_final'][0] == 'vpq_all:100.0000', j['vpq_final']
-
-
-# ---------------------------------------------------------------------------------------------------------------------------------
-# The reference's own caller. mmcv is absent: `MMDataParallel` / `DataContainer` are restated here with the behaviour the call
-# relies on (mmcv 0.2.x parallel/data_container.py, scatter_gather.py: a cpu_only container is unwrapped to its per-GPU list, tensors
-# are moved to the device, lists are mapped element-wise); every kernel launch is the recording stub of tests/test_host_dryrun.py.
-# ---------------------------------------------------------------------------------------------------------------------------------
-class DataContainer:
-    def __init__(self, data, stack=False, padding_value=0, cpu_only=False):
-        self._data, self.stack, self.cpu_only = data, stack, cpu_only
-
-    data = property(lambda s: s._data)
-
-
-class MMDataParallel(torch.nn.Module):
-    def __init__(self, module, device_ids=None, to_device=None):
-        super().__init__()
-        self.module, self.device_ids, self._to = module, device_ids, to_device
-
-    def _scatter(self, obj):
-        if isinstance(obj, DataContainer):
-            return obj.data[0] if obj.cpu_only else self._scatter(obj.data[0])
-        if torch.is_tensor(obj):
-            return self._to(obj)
-        if isinstance(obj, (list, tuple)):
-            return type(obj)(self._scatter(o) for o in obj)
-        if isinstance(obj, dict):
-            return {k: self._scatter(v) for k, v in obj.items()}
-        return obj
-
-    def forward(self, *inputs, **kwargs):
-        return self.module(*self._scatter(inputs), **self._scatter(kwargs))
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason='the reference tree exists in the build container only')
-def test_reference_single_gpu_test_drives_the_plugin():
-    """in a child process: the import shims patch torch globally (`.cuda()` no-ops, ...)"""
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), 'ref_caller'], capture_output=True, text=True, timeout=900,
-                       env=dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, 'tests')])))
-    assert p.returncode == 0 and 'REF_CALLER_OK' in p.stdout, (p.stdout[-1500:], p.stderr[-3000:])
-
-
-def _ref_caller_main():
-    from test_host_dryrun import _FakeCuda, _RecordingLib
-    sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
-    import ref_shims
-    ref_shims.install()
-    # INTEGRATION.md Level 1: the maintainer's one-line change - build_detector comes from vps_amd
-    sys.modules['mmdet.models'].build_detector = vps_amd.build_detector
-    sys.modules['mmcv.parallel'].MMDataParallel = MMDataParallel
-    sys.modules['mmcv.runner'].load_checkpoint = vps_amd.load_checkpoint
-    ref_shims._stub('tools.dataset')                                 # `from tools.dataset import *`: the evaluation helpers (main() only)
-    spec = importlib.util.spec_from_file_location('ref_test_vpq', os.path.join(REF, 'tools', 'test_vpq.py'))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)                                     # the REAL tools/test_vpq.py
-    assert ref.build_detector is vps_amd.build_detector and ref.MMDataParallel is MMDataParallel
-
-    lib = _RecordingLib()
-    hip.load = lambda: lib
-    hip.ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-    hip.stream_ptr = lambda: None
-    hip.conv2d = lambda d: lib.called.add('vps_conv2d')
-    cfg = vps_amd.Config.fromfile(os.path.join(ROOT, 'configs', 'cityscapes', 'fusetrack.py'))
-    model = ref.build_detector(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)          # test_vpq.py:129-131
-    model.overlap_streams = False
-    synth.load_synth(model, 0)
-    model.CLASSES = ('person', 'rider', 'car', 'truck', 'bus', 'train', 'motorcycle', 'bicycle')
-    H, W = 128, 256
-    frames = synth.synth_clip(H, W, 3, 0)
-
-    class Loader:                         # what build_dataloader(...) yields in test mode (MultiScaleFlipAug + Collect, imgs_per_gpu=1)
-        dataset = list(range(3))
-
-        def __iter__(self):
-            for t in range(3):
-                meta = synth.img_meta(H, W, 10001 + t)
-                meta['filename'] = 'data/cityscapes_vps/val/img_all/0000_%04d_frankfurt_000000_%06d_newImg8bit.png' % (t, t)
-                yield dict(img=[frames[t]], img_meta=[DataContainer([[meta]], cpu_only=True)], ref_img=[frames[t - 1 if t else 0]])
-
-    wrapped = ref.MMDataParallel(model, device_ids=[0], to_device=lambda t: t.as_subclass(_FakeCuda))      # test_vpq.py:149
-    # (the loader wrapped the way vps_amd.build_dataloader does it: the reference's loop iterates the look-ahead loader unchanged)
-    results, pano = ref.single_gpu_test(wrapped, vps_amd.LookaheadLoader(Loader(), depth=2, device=None))       # test_vpq.py:28-69
-    assert len(results) == 3 and all(len(r) == 2 for r in results)
-    assert pano['all_names'] == ['0000_%04d_frankfurt_000000_%06d_newImg8bit.png' % (t, t) for t in range(3)]
-    for k in ('all_ssegs', 'all_panos'):
-        assert len(pano[k]) == 3 and all(a.dtype == np.uint8 and a.shape == (H, W) for a in pano[k])
-    assert len(pano['all_pano_cls_inds']) == 3 and len(pano['all_pano_obj_ids']) == 3
-    assert all(len(a) == len(b) for a, b in zip(pano['all_pano_cls_inds'], pano['all_pano_obj_ids']))
-    assert isinstance(results[0][0], dict)                            # bbox2result_with_id: id-keyed boxes
-    assert 'vps_conv2d' in lib.called and 'vps_panoptic_combine_dev' in lib.called
-    print('REF_CALLER_OK')
-
-
-if __name__ == '__main__' and sys.argv[1:] == ['ref_caller']:
-    _ref_caller_main()

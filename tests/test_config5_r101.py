@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_npz
 import vps_amd
 from vps_amd import synth
 
@@ -54,7 +55,7 @@ def _build(prec=None):
 
 
 def test_r101_state_dict_matches_reference_module_tree():
-    g = np.load(GOLD)
+    g = golden_npz.load(GOLD)
     manifest = json.loads(bytes(g['state_dict_manifest']).decode())
     cfg = vps_amd.Config.fromfile(CFG)
     m = vps_amd.build_detector(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)
@@ -65,7 +66,7 @@ def test_r101_state_dict_matches_reference_module_tree():
 
 def test_r101_oracle_matches_reference():
     from oracle.fusetrack import FuseTrackOracle
-    g = np.load(GOLD)
+    g = golden_npz.load(GOLD)
     H, W, n, seed = [int(v) for v in g['meta']]
     cfg = vps_amd.Config.fromfile(CFG)
     m = vps_amd.build_detector(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)
@@ -87,7 +88,7 @@ def test_r101_oracle_matches_reference():
 @pytest.mark.gpu
 @pytest.mark.parametrize('prec', ['f32', 'f16x3', 'bf16'])
 def test_r101_hip_matches_reference_golden(dev, prec):
-    g = np.load(GOLD)
+    g = golden_npz.load(GOLD)
     H, W, n, seed = [int(v) for v in g['meta']]
     m, _ = _build(prec)
     fr = synth.synth_clip(H, W, n, seed)

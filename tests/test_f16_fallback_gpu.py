@@ -18,6 +18,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import golden_npz
 import vps_amd
 from vps_amd import hip, nhwc, synth
 
@@ -53,7 +54,7 @@ def test_layer_reports_and_falls_back_to_bf16x6(dev):
 
 
 def test_range_shifted_checkpoint_runs_in_f16x3_with_one_layer_on_bf16x6(dev):
-    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'fusetrack_clip.npz'))
+    g = golden_npz.load(os.path.join(ROOT, 'tests', 'golden', 'fusetrack_clip.npz'))
     H, W, n, seed = [int(v) for v in g['meta']]
     old = nhwc.DEFAULT_PREC
     nhwc.DEFAULT_PREC = hip.PREC_F16X3

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_npz
 import tolerances as T
 import vps_amd
 from vps_amd import hip, nhwc, synth
@@ -185,7 +186,7 @@ def _class_map(pan, cls_inds):
 
 @pytest.mark.parametrize('prec_name', ['f32', 'bf16x6', 'f16x3'])
 def test_full_size_outputs_match_reference_golden(dev, prec_name):
-    g = np.load(GOLD_FULL)
+    g = golden_npz.load(GOLD_FULL)
     gh, gw, n, seed = [int(v) for v in g['meta']]
     assert (gh, gw) == (H, W)
     s1, s2, c5 = [int(v) for v in g['strides']]
@@ -289,7 +290,7 @@ GOLD_COND = os.path.join(ROOT, 'tests', 'golden', 'fusetrack_fullsize_cond.npz')
 # (profiles/r06_fullsize_conditioned_bf16_bf16x3_report.txt).
 @pytest.mark.parametrize('prec_name', ['f16x3', 'bf16x6', 'f32', 'bf16x3'])
 def test_every_stage_within_1e_4_of_the_reference_on_the_conditioned_checkpoint(dev, prec_name):
-    g = np.load(GOLD_COND)
+    g = golden_npz.load(GOLD_COND)
     tol = T.CONDITIONED_BF16X3 if prec_name == 'bf16x3' else T.CONDITIONED
     gh, gw, n, seed = [int(v) for v in g['meta']]
     assert (gh, gw) == (H, W)

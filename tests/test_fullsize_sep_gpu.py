@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_npz
 import tolerances as T
 import vps_amd
 from vps_amd import hip, nhwc, synth
@@ -58,7 +59,7 @@ def _rel(a, b):
 @pytest.mark.parametrize('prec_name', ['f16x3', 'bf16x6', 'f32'])
 def test_strict_full_size_parity_on_the_separated_fixture(dev, prec_name, fixture):
     gold, head, nfr, hw, cfg_path = FIXTURES[fixture]
-    g = np.load(gold)
+    g = golden_npz.load(gold)
     H, W, n, seed = [int(v) for v in g['meta']]
     s1, s2, c5 = [int(v) for v in g['strides']]
     ms = int(g['map_stride']) if 'map_stride' in g.files else 1

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_npz
 import tolerances as T
 import vps_amd
 from vps_amd import nhwc, synth
@@ -31,7 +32,7 @@ def setup(dev, request):
     """every test of this module runs in ALL fp32-grade arithmetic modes: the exact-fp32 MFMA kernels (library default), the
     split-bf16x6 kernels and the split-fp16x3 kernels (VPS_PREC=bf16x6 / f16x3)"""
     from vps_amd import hip, nhwc
-    gold = np.load(GOLD)
+    gold = golden_npz.load(GOLD)
     H, W, n, seed = [int(v) for v in gold['meta']]
     cfg = vps_amd.Config.fromfile(os.path.join(ROOT, 'configs', 'cityscapes', 'fusetrack.py'))
     old = nhwc.DEFAULT_PREC
@@ -51,7 +52,7 @@ def setup(dev, request):
 def oracle_clip():
     """the oracle on the golden clip, computed once for both arithmetic modes"""
     from oracle.fusetrack import FuseTrackOracle
-    gold = np.load(GOLD)
+    gold = golden_npz.load(GOLD)
     H, W, n, seed = [int(v) for v in gold['meta']]
     cfg = vps_amd.Config.fromfile(os.path.join(ROOT, 'configs', 'cityscapes', 'fusetrack.py'))
     model = vps_amd.build_detector(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)

@@ -16,6 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import golden_npz
 import inject_cases as IC
 import vps_amd
 from oracle import fusetrack as OF
@@ -32,7 +33,7 @@ def ctx():
     cfg = vps_amd.Config.fromfile(os.path.join(ROOT, 'configs', 'cityscapes', 'fusetrack.py'))
     model = vps_amd.build_detector(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)
     sd = synth.synth_state_dict({k: v.shape for k, v in model.state_dict().items()}, 0)
-    return sd, IC.neck_features(), np.load(GOLD)
+    return sd, IC.neck_features(), golden_npz.load(GOLD)
 
 
 def _canonical(scores, rois, keep, pano, bbox_ids, pan_map, first_frame):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_npz
 import vps_amd
 from oracle.fusetrack import FuseTrackOracle
 from vps_amd import synth
@@ -23,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # two golden clips of the real reference FuseTrack: weight / clip seed 0 at 128x256 and seed 1 at 128x192 (make_golden.py seed1)
 @pytest.fixture(scope='module', params=['fusetrack_clip.npz', 'fusetrack_clip_seed1.npz'], ids=['seed0', 'seed1'])
 def gold(request):
-    return np.load(os.path.join(os.path.dirname(GOLD), request.param))
+    return golden_npz.load(os.path.join(os.path.dirname(GOLD), request.param))
 
 
 @pytest.fixture(scope='module')
@@ -54,7 +55,7 @@ def test_state_dict_keys_match_reference_module_tree(variant, gold_file):
     """the drop-in checkpoint contract: the key -> shape manifest of the REAL reference module tree, stored in the
     golden file by make_golden.py, equals the state_dict of the vps_amd detector built from the same config"""
     import json
-    g = np.load(os.path.join(ROOT, 'tests', 'golden', gold_file))
+    g = golden_npz.load(os.path.join(ROOT, 'tests', 'golden', gold_file))
     manifest = json.loads(bytes(g['state_dict_manifest']).decode())
     cfg = vps_amd.Config.fromfile(os.path.join(ROOT, 'configs', 'cityscapes', variant + '.py'))
     model = vps_amd.build_detector(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)
@@ -141,7 +142,7 @@ def test_tolerant_golden_comparison_accepts_the_oracle_and_a_relabelling_and_rej
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope='module')
 def full_gold():
-    return np.load(os.path.join(ROOT, 'tests', 'golden', 'fusetrack_fullsize.npz'))
+    return golden_npz.load(os.path.join(ROOT, 'tests', 'golden', 'fusetrack_fullsize.npz'))
 
 
 @pytest.fixture(scope='module')
@@ -192,7 +193,7 @@ def test_fullsize_oracle_matches_reference(full_gold, full_oracle_run, t):
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope='module')
 def sep_gold():
-    return np.load(os.path.join(ROOT, 'tests', 'golden', 'fusetrack_fullsize_sep.npz'))
+    return golden_npz.load(os.path.join(ROOT, 'tests', 'golden', 'fusetrack_fullsize_sep.npz'))
 
 
 @pytest.fixture(scope='module')
@@ -250,7 +251,7 @@ def test_dense_fixture_margins_are_what_the_file_says():
     m, req = z['margins'], z['required']              # per frame: detections, |score - 0.6| min, adjacent score gap min, |IoU - 0.5| min
     assert m.shape == (6, 4) and (m[:, 0] >= 30).all() and m[0, 0] >= 50
     assert m[:, 1].min() >= req[0] >= 1e-2 and m[:, 2].min() >= req[1] >= 2.5e-3 and m[:, 3].min() >= req[2] >= 2e-2
-    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'fusetrack_fullsize_dense.npz'))
+    g = golden_npz.load(os.path.join(ROOT, 'tests', 'golden', 'fusetrack_fullsize_dense.npz'))
     kept = [len(g['f%d.panoptic_cls_inds' % t]) for t in range(6)]
     ids = [g['f%d.panoptic_det_obj_ids' % t] for t in range(6)]
     assert min(kept) >= 30 and max(int(i.max()) for i in ids) >= 60
@@ -263,7 +264,7 @@ def test_dense_fixture_margins_are_what_the_file_says():
 
 
 def test_dense_fullsize_oracle_matches_reference():
-    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'fusetrack_fullsize_dense.npz'))
+    g = golden_npz.load(os.path.join(ROOT, 'tests', 'golden', 'fusetrack_fullsize_dense.npz'))
     H, W, n, seed = [int(v) for v in g['meta']]
     ms = int(g['map_stride'])
     assert (H, W, n) == (1024, 2048, 6)
@@ -299,7 +300,7 @@ def test_config5_fixture_files_are_consistent():
     m, req = z['margins'], z['required']
     assert m.shape == (3, 4) and (m[:, 0] >= 4).all()
     assert m[:, 1].min() >= req[0] >= 2e-2 and m[:, 2].min() >= req[1] >= 2e-2 and m[:, 3].min() >= req[2] >= 4e-2
-    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'fusetrack_config5_sep.npz'))
+    g = golden_npz.load(os.path.join(ROOT, 'tests', 'golden', 'fusetrack_config5_sep.npz'))
     assert [int(v) for v in g['meta']][:3] == [1088, 1920, 3]
     kept = [len(g['f%d.panoptic_cls_inds' % t]) for t in range(3)]
     assert kept == z['kept'].tolist() and kept == [int(v) for v in m[:, 0]]       # the real reference keeps what the oracle kept when the layer was chosen
@@ -314,7 +315,7 @@ def test_config5_fixture_files_are_consistent():
 
 @pytest.mark.skipif(not os.environ.get('VPS_SLOW_TESTS'), reason='~10 min of CPU: VPS_SLOW_TESTS=1')
 def test_config5_oracle_matches_reference():
-    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'fusetrack_config5_sep.npz'))
+    g = golden_npz.load(os.path.join(ROOT, 'tests', 'golden', 'fusetrack_config5_sep.npz'))
     H, W, n, seed = [int(v) for v in g['meta']]
     ms = int(g['map_stride'])
     cfg = vps_amd.Config.fromfile(os.path.join(ROOT, 'configs', 'viper', 'fusetrack_r101.py'))

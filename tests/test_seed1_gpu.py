@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_npz
 import vps_amd
 from vps_amd import synth
 
@@ -21,7 +22,7 @@ GOLD = os.path.join(ROOT, 'tests', 'golden', 'fusetrack_clip_seed1.npz')
 def test_second_seed_clip_matches_reference_golden(dev, prec):
     from golden_compare import compare_frame
     from vps_amd import nhwc
-    g = np.load(GOLD)
+    g = golden_npz.load(GOLD)
     H, W, n, seed = [int(v) for v in g['meta']]
     assert (H, W, seed) == (128, 192, 1)
     cfg = vps_amd.Config.fromfile(os.path.join(ROOT, 'configs', 'cityscapes', 'fusetrack.py'))

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_npz
 import vps_amd
 from oracle.fusetrack import FuseTrackOracle
 from vps_amd import synth
@@ -17,7 +18,7 @@ VARIANTS = {'fuse': dict(with_fusion=True, with_track=False), 'track': dict(with
 
 
 def _gold(v):
-    return np.load(os.path.join(ROOT, 'tests', 'golden', '%s_clip.npz' % v))
+    return golden_npz.load(os.path.join(ROOT, 'tests', 'golden', '%s_clip.npz' % v))
 
 
 def _model(v):

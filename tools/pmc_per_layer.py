@@ -1,6 +1,6 @@
 """Per-layer HBM-side traffic of the conv launches of ONE frame: joins the launch order of bench.py's instrumented frame
 (`--conv-table X` writes X.ordered.json) with the per-dispatch rows of the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE)
-of `bench.py --steps 1 --warmup 1 --single-stream` — the instrumented frame is the last frame of that command, one stream, so
+of `bench.py --full --steps 1 --warmup 1 --single-stream` — the instrumented frame is the last frame of that command, one stream, so
 its conv dispatches are the last len(order) conv dispatches of the trace, in order; a split-K reduce kernel is charged to the conv
 launch in front of it. Units and the gfx950 FETCH_SIZE correction as in tools/pmc_traffic.py.
 

@@ -1,16 +1,16 @@
 """Aggregate the HBM-side traffic of the conv kernels from two rocprofv3 --pmc passes over bench.py (GPU box).
 
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/pmc_fetch -o pmc -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/pmc_write -o pmc -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline
-    python $R/tools/pmc_traffic.py $R/gpurun_out/pmc_fetch $R/gpurun_out/pmc_write 3 > $R/gpurun_out/pmc_traffic.json
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/out/pmc_fetch -o pmc -- python $R/bench.py --full --steps 1 --warmup 1 --single-stream --no-cpu-baseline --no-extras
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $R/out/pmc_write -o pmc -- python $R/bench.py --full --steps 1 --warmup 1 --single-stream --no-cpu-baseline --no-extras
+    python $R/tools/pmc_traffic.py $R/out/pmc_fetch $R/out/pmc_write 7 > $R/out/pmc_traffic.json
 
 (separate passes, no other trace domain: MI355X_MICROARCH.md "HBM" / "rocprofv3 PMC slots"). FETCH_SIZE / WRITE_SIZE are
 in KiB; on gfx950 FETCH_SIZE counts 128-byte requests of wide (16 B/lane) coalesced reads as 64 bytes, so it is doubled
 (all loads of the conv kernels are global_load_dwordx4 / buffer_load_dwordx4); WRITE_SIZE is taken as reported (uncalibrated, see the guide).
 The third argument is the number of frames the profiled command ran: warmup + steps + the 2 set-up frames and the 3 instrumented
-frames of bench.py's single-stream section (7 for `--steps 1 --warmup 1`; 5 up to round 5's committed measurement, which ran one
-instrumented frame)."""
+frames of bench.py's single-stream section, which runs with --full only (7 for `--full --steps 1 --warmup 1`; 5 up to round 5's
+committed measurement, which ran one instrumented frame)."""
 import csv
 import re
 import glob

@@ -3,28 +3,29 @@
 # more than one MI355X:
 #     bash tools/run_scale.sh            # N = 1 2 4 8 (those the node has), weak scaling (K frames per rank) + the fixed 30-frame clip
 #     NS="1 2" STEPS=50 bash tools/run_scale.sh
-# Every run is `python bench.py --gpus N`: for N > 1 bench.py re-launches itself under torch.distributed.run (one rank per GPU, RCCL
+# Every run is `python bench.py --full --gpus N`: for N > 1 bench.py re-launches itself under torch.distributed.run (one rank per GPU, RCCL
 # over xGMI, rendezvous on 127.0.0.1) and rank 0 prints ONE JSON line carrying `n_gpus`, `rccl_ranks` (all-reduce of ones), `value`
 # (whole-job frames/s, weak) and `clip30` (the 30-frame clip sharded over the N GPUs: strong scaling, id checksum). Lines go to
-# gpurun_out/scale_N<N>.json; the table at the end is computed from them (efficiency = value_N / (N * value_1)). The clip30 id
+# $OUT/scale_N<N>.json (default out/); the table at the end is computed from them (efficiency = value_N / (N * value_1)). The clip30 id
 # checksum must be the same for every N: the sharded pipeline reproduces the sequential ids.
 set -u
 cd "$(dirname "$0")/.."
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-mkdir -p gpurun_out
+export OUT=${OUT:-out}
+mkdir -p $OUT
 NS=${NS:-"1 2 4 8"}; STEPS=${STEPS:-100}; WARMUP=${WARMUP:-5}
 NDEV=$(python -c "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)")
 echo "devices visible: $NDEV"
 for N in $NS; do
     if [ "$N" -gt "$NDEV" ]; then echo "N=$N skipped: the node has $NDEV GPU(s)"; continue; fi
     extra="--no-cpu-baseline"; [ "$N" = "1" ] && extra=""
-    timeout 1200 python bench.py --gpus $N --steps $STEPS --warmup $WARMUP $extra > gpurun_out/scale_N$N.json 2> gpurun_out/scale_N$N.err
-    echo "N=$N rc=$? $(head -c 160 gpurun_out/scale_N$N.json)"
+    timeout 1200 python bench.py --full --gpus $N --steps $STEPS --warmup $WARMUP $extra > $OUT/scale_N$N.json 2> $OUT/scale_N$N.err
+    echo "N=$N rc=$? $(head -c 160 $OUT/scale_N$N.json)"
 done
 python - <<'PY'
-import glob, json, re
+import glob, json, os, re
 rows = {}
-for f in sorted(glob.glob('gpurun_out/scale_N*.json')):
+for f in sorted(glob.glob(os.path.join(os.environ['OUT'], 'scale_N*.json'))):
     try:
         j = json.loads(open(f).read().strip().splitlines()[-1])
     except Exception as e:
