@@ -371,6 +371,28 @@ int vps_panoptic_combine_dev(const float* fcn_score, int score_ld, int Hs, int W
 int vps_png_info(const uint8_t* file, int64_t nbytes, int32_t* H, int32_t* W, int32_t* channels);
 int vps_png_decode_bgr8(const uint8_t* file, int64_t nbytes, uint8_t* out, int64_t out_capacity);
 
+/* JPEG input (the VIPER frames). The Huffman bit stream is decoded on the HOST (two functions, no device work, no stream, no
+ * interpreter lock, no allocation); dequantisation, the 8x8 inverse DCT, chroma upsampling and YCbCr -> BGR run on the DEVICE and are
+ * bit-exact with libjpeg's default decode (slow-integer IDCT, fancy upsampling, 16-bit fixed-point colour) - what cv2.imread and PIL
+ * compute.
+ * vps_jpeg_info: geometry of an 8-bit Huffman-coded sequential JPEG (SOF0 / SOF1, one interleaved scan) with 1 component or 3 YCbCr
+ * components sampled 4:4:4, 4:2:2 (h2v1) or 4:2:0 (h2v2). samp [3][2] = (h, v) sampling factors, grid [3][2] = (block rows, block
+ * columns) of each component padded to whole MCUs, qt [3][64] = each component's quantisation table in natural (row-major) order,
+ * coef_bytes = what vps_jpeg_decode_coef writes; a grey file repeats its component in entries 1 and 2. Every output pointer may be
+ * NULL. Progressive / lossless / arithmetic / 12-bit files, other component counts or colour spaces (Adobe APP14), other sampling,
+ * an EXIF orientation other than 1 (cv2.imread rotates such files, PIL does not) and a scan that does not end in EOI return an
+ * argument error: the caller uses its general decoder.
+ * vps_jpeg_decode_coef: quantised coefficients, int16 [component][block row][block column][64] in natural order, DC prediction
+ * undone, NOT dequantised; capacity in bytes >= coef_bytes. A damaged bit stream returns an argument error.
+ * vps_jpeg_reconstruct (device; launches on `stream`, no sync, no hidden allocation): coef and qt are DEVICE pointers (16-byte
+ * aligned), H / W / ncomp / samp / grid (host arrays) as vps_jpeg_info reported them, ws = device workspace for the sample planes,
+ * ws_bytes >= coef_bytes / 2; out = uint8 [H][W][3] BGR cropped to the true size (a grey file replicated, like IMREAD_COLOR). */
+int vps_jpeg_info(const uint8_t* file, int64_t nbytes, int32_t* H, int32_t* W, int32_t* ncomp, int32_t* samp, int32_t* grid,
+                  uint16_t* qt, int64_t* coef_bytes);
+int vps_jpeg_decode_coef(const uint8_t* file, int64_t nbytes, int16_t* coef, int64_t capacity);
+int vps_jpeg_reconstruct(const int16_t* coef, const uint16_t* qt, int H, int W, int ncomp, const int32_t* samp, const int32_t* grid,
+                         uint8_t* ws, int64_t ws_bytes, uint8_t* out, void* stream);
+
 /* ref: models/anchor_heads/rpn_head.py:62-91 (sigmoid objectness, `scores.topk(nms_pre)`, gathers) + core/anchor/anchor_generator.py:55-72
  * (grid anchors) + core/bbox/transforms.py:34-68 (delta2bbox, means 0, clipped to the image) for ALL levels: one chip-wide scoring
  * launch + one select / sort / decode launch with one workgroup per level. cls[l] / reg[l]: NHWC maps [H_l][W_l][ld] of level l

@@ -12,6 +12,15 @@ host threads the decode needs to keep up. Prints one JSON line. The GPU part is 
 
     python tools/bench_input_pipeline.py --node 8 --threads 6 [--seconds 8]
 
+    python tools/bench_input_pipeline.py --format jpeg [--height 1080 --width 1920] [--workers 1 2 4 8] [--out FILE]
+
+JPEG mode (the VIPER frames, 1080x1920 by default): the same run times both decode legs at each worker count - `native`, what a
+`ClipFeeder` worker does for a .jpg (`vps_jpeg_decode_coef` into a reused staging buffer; the pixels are rebuilt on the device), and
+`imread`, the route such a file took before (PIL: full decode + RGB->BGR copy). With a GPU it adds `vps_jpeg_reconstruct` timed by
+events (median of 30 launches) beside its 12.5 MB of algorithmic traffic at 8 TB/s, and a `ClipFeeder` drained by an otherwise idle
+consumer. The gain of the native path is host CPU time and pinned pixel semantics; the device stage is microseconds off the model's
+critical path.
+
 NODE mode (round 6): what the host of an 8-GPU node has to deliver - `--node` decoder PROCESSES (one per rank, as
 `bench.py --gpus 8` starts them), each with the thread budget of a rank's `ClipFeeder` (`--threads`, default 6) and pinned to its own
 block of cores (os.sched_setaffinity: cores [r * C/8, (r+1) * C/8) - a rank's decode threads stay on the cores next to its GPU and
@@ -103,17 +112,116 @@ def node_mode(args):
     print(json.dumps(out))
 
 
+def jpeg_mode(args):
+    import ctypes
+    import threading
+    import warnings
+    import torch
+    from PIL import Image
+    from vps_amd import hip, synth
+    from vps_amd.pipeline import JPEG_QT_BYTES, ClipFeeder, DeviceImagePrep, imread, jpeg_info, jpeg_reconstruct
+    H, W = args.height, args.width
+    tmp = tempfile.mkdtemp(prefix='vps_input_')
+    files = []
+    for t in range(args.frames):
+        fr = synth.synth_frame(H, W, seed=t % 4, shift=(2 * (t % 8), t % 8), noise=2.0).astype(np.uint8)
+        fn = os.path.join(tmp, 'f%04d.jpg' % t)
+        Image.fromarray(np.ascontiguousarray(fr[:, :, ::-1])).save(fn, quality=90, subsampling=2)
+        files.append(fn)
+    lib = hip.load_host()
+    ji = jpeg_info(bytearray(open(files[0], 'rb').read()))
+    assert ji is not None
+    out = dict(mode='jpeg', frames=args.frames, size=[H, W], jpeg_MB_per_frame=round(sum(os.path.getsize(f) for f in files) / 1e6 / len(files), 3),
+               coef_MB_per_frame=round(ji.coef_bytes / 1e6, 2), host_cpus=os.cpu_count(), native_frames_per_s={}, imread_frames_per_s={},
+               legs='native = file read + vps_jpeg_decode_coef into a reused staging buffer (a ClipFeeder worker); imread = file read + PIL decode '
+                    '+ BGR copy (the route of a .jpg before the native path)')
+    local = threading.local()
+
+    def native(fn):
+        if not hasattr(local, 'stage'):
+            local.stage = np.empty(ji.coef_bytes + JPEG_QT_BYTES, dtype=np.uint8)
+        data = bytearray(open(fn, 'rb').read())
+        cbuf = (ctypes.c_char * len(data)).from_buffer(data)
+        hip.check(lib.vps_jpeg_decode_coef(cbuf, len(data), local.stage.ctypes.data_as(ctypes.c_void_p), ji.coef_bytes), 'vps_jpeg_decode_coef')
+
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        for nw in args.workers:
+            for name, fn in (('native_frames_per_s', native), ('imread_frames_per_s', imread)):
+                with ThreadPoolExecutor(nw) as ex:
+                    list(ex.map(fn, files[:nw]))                   # warm-up
+                    t0 = time.perf_counter()
+                    list(ex.map(fn, files))
+                    out[name][str(nw)] = round(len(files) / (time.perf_counter() - t0), 1)
+        if torch.cuda.is_available():
+            dev = torch.device('cuda:0')
+            data = bytearray(open(files[0], 'rb').read())
+            host = torch.empty(ji.coef_bytes + JPEG_QT_BYTES, dtype=torch.uint8).pin_memory()
+            hip.check(lib.vps_jpeg_decode_coef((ctypes.c_char * len(data)).from_buffer(data), len(data), ctypes.c_void_p(host.data_ptr()), ji.coef_bytes),
+                      'vps_jpeg_decode_coef')
+            host[ji.coef_bytes:].copy_(torch.from_numpy(ji.qt.view(np.uint8).reshape(-1)))
+            buf = host.to(dev)
+            ws = torch.empty(ji.coef_bytes // 2, dtype=torch.uint8, device=dev)
+            for _ in range(5):
+                jpeg_reconstruct(buf, ji, ws)
+            torch.cuda.synchronize()
+            ms = []
+            for _ in range(30):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); jpeg_reconstruct(buf, ji, ws); e1.record()
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1))
+            med = float(np.median(ms))
+            traffic = ji.coef_bytes + H * W * 3
+            out['reconstruct_ms_median_of_30'] = round(med, 4)
+            out['reconstruct_algorithmic_MB'] = round(traffic / 1e6, 2)
+            out['reconstruct_fraction_of_8TBps'] = round(traffic / 8e12 / (med * 1e-3), 4)
+            prep = DeviceImagePrep(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True, size_divisor=32,
+                                   img_scale=(max(H, W), min(H, W)), device=dev)
+            out['feeder_frames_per_s'] = {}
+            for nw in args.workers:
+                fd = ClipFeeder(files, prep, workers=nw)
+                fd(0); torch.cuda.synchronize()                    # ring allocation + first decode outside the timing
+                t0 = time.perf_counter()
+                for t in range(1, len(files)):
+                    fd(t)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                fd.close()
+                assert fd.native_jpeg == len(files) and fd.fallback_decodes == 0
+                out['feeder_frames_per_s'][str(nw)] = dict(frames_per_s=round((len(files) - 1) / dt, 1),
+                                                           wait_for_decode_s=round(fd.stats['wait_for_decode_s'], 4),
+                                                           upload_prep_s=round(fd.stats['upload_prep_s'], 4))
+            out['feeder_note'] = 'consumer = fd(t) in a loop on an otherwise idle main thread (no detector beside it)'
+    for f in files:
+        os.remove(f)
+    os.rmdir(tmp)
+    line = json.dumps(out)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(line + '\n')
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=48)
     ap.add_argument('--workers', type=int, nargs='+', default=[1, 2, 4, 8, 16])
-    ap.add_argument('--height', type=int, default=1024)
-    ap.add_argument('--width', type=int, default=2048)
+    ap.add_argument('--format', choices=['png', 'jpeg'], default='png', help='jpeg: native entropy decode against the PIL route, 1080x1920 frames')
+    ap.add_argument('--height', type=int, default=None, help='default 1024 (png, Cityscapes-VPS) / 1080 (jpeg, VIPER)')
+    ap.add_argument('--width', type=int, default=None, help='default 2048 (png) / 1920 (jpeg)')
+    ap.add_argument('--out', default=None, help='jpeg mode: also write the JSON line to this file')
     ap.add_argument('--node', type=int, default=0, help='node mode: this many rank processes decode concurrently')
     ap.add_argument('--threads', type=int, default=6, help='node mode: decode threads per rank (ClipFeeder workers)')
     ap.add_argument('--seconds', type=float, default=8.0)
     ap.add_argument('--need', type=float, default=56.0, help='node mode: frames/s one GPU consumes')
     args = ap.parse_args()
+    if args.height is None:
+        args.height = 1080 if args.format == 'jpeg' else 1024
+    if args.width is None:
+        args.width = 1920 if args.format == 'jpeg' else 2048
+    if args.format == 'jpeg':
+        return jpeg_mode(args)
     if args.node:
         return node_mode(args)
     import torch

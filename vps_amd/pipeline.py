@@ -135,8 +135,10 @@ class ClipFeeder:
     library's own PNG decoder (`csrc/png_host.cpp`, a C-ABI call that runs without the interpreter lock) writes the BGR frame
     STRAIGHT INTO A PINNED staging buffer of a small ring - no per-frame host allocation, no copy on the consumer's thread. The
     consumer uploads the uint8 frame (6 MB instead of the 25 MB fp32 tensor) and `DeviceImagePrep.prep` makes the normalised,
-    padded fp32 tensor on the device. Files the native decoder does not take (JPEG, 16-bit / palette PNG) go through `imread` and one
-    copy into the staging buffer. What did NOT work (measured on the GPU box): PIL decode threads - they hold the interpreter lock
+    padded fp32 tensor on the device. A baseline JPEG (the VIPER frames) is entropy-decoded by the worker the same way (`csrc/jpeg_host.cpp`): the slot then holds
+    its quantised coefficients, and the consumer's upload is followed by `vps_jpeg_reconstruct` (inverse DCT, upsampling, colour
+    on the device; bit-exact with libjpeg, so with cv2.imread). Files the native decoders do not take (progressive / CMYK JPEG, 16-bit
+    / palette PNG) go through `imread` and one copy into the staging buffer (`fallback_decodes`). What did NOT work (measured on the GPU box): PIL decode threads - they hold the interpreter lock
     for long stretches and beside a main thread that launches ~560 kernels per frame deliver 6 frames/s; forked decode processes -
     the fork of a process that maps 30 GB of device memory stalls (1.4 frames/s). A prepared frame is kept until the consumer asks
     for a frame two positions later (frame t is frame t+1's reference), so the same tensor OBJECT serves as `img` of frame t and
@@ -161,6 +163,8 @@ class ClipFeeder:
         self._next = 0              # first index not yet submitted
         self._hi = len(self.files)  # the window never runs past this frame (`set_range`: the end of a rank's shard)
         self.decodes = 0
+        self.native_jpeg = 0        # frames whose entropy decode ran in the library and whose pixels the device reconstructed
+        self.fallback_decodes = 0   # frames that went through `imread` (files the native decoders do not take)
         self.out_of_window = 0      # requests that found their frame neither prepared nor in flight (decoded on the spot)
         self.stats = dict(wait_for_decode_s=0.0, upload_prep_s=0.0)      # where the consumer's time in __call__ went
         self._stage, self._fbuf, self._events = [], [], []
@@ -184,7 +188,9 @@ class ClipFeeder:
         self._events = [None] * n
 
     def _decode(self, path, slot):
-        """worker thread: file -> staging slot; returns the frame's (H, W)"""
+        """worker thread: file -> staging slot; returns (H, W, tag): tag None = the slot holds the BGR frame, 'imread' = the same
+        through the general decoder, a `JpegInfo` = the slot holds a JPEG's coefficients + quantisation tables (the device
+        reconstructs the frame: `jpeg_reconstruct`)"""
         lib = hip.load_host()
         size = osp.getsize(path)
         if len(self._fbuf[slot]) < size:
@@ -195,14 +201,21 @@ class ClipFeeder:
         stage = self._stage[slot]
         cbuf = (ctypes.c_char * len(buf)).from_buffer(buf)
         H, W, C = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-        if str(path).lower().endswith('.png') and lib.vps_png_info(cbuf, n, ctypes.byref(H), ctypes.byref(W), ctypes.byref(C)) == 0 \
+        low = str(path).lower()
+        if low.endswith('.png') and lib.vps_png_info(cbuf, n, ctypes.byref(H), ctypes.byref(W), ctypes.byref(C)) == 0 \
                 and H.value * W.value * 3 <= stage.numel():
             hip.check(lib.vps_png_decode_bgr8(cbuf, n, ctypes.c_void_p(stage.data_ptr()), stage.numel()), 'vps_png_decode_bgr8')
-            return H.value, W.value
+            return H.value, W.value, None
+        if low.endswith(('.jpg', '.jpeg')) and self.prep.device.type == 'cuda':      # the reconstruction has no CPU twin: host stand-ins use imread
+            ji = jpeg_info(cbuf, n)
+            if ji is not None and ji.coef_bytes + JPEG_QT_BYTES <= stage.numel() \
+                    and lib.vps_jpeg_decode_coef(cbuf, n, ctypes.c_void_p(stage.data_ptr()), ji.coef_bytes) == 0:
+                stage[ji.coef_bytes:ji.coef_bytes + JPEG_QT_BYTES].copy_(torch.from_numpy(ji.qt.view(np.uint8).reshape(-1)))
+                return ji.H, ji.W, ji
         img = imread(path)                         # the general decoder (cv2 / PIL) + one copy
         assert img.nbytes <= stage.numel(), 'frame larger than the staging buffer (%d > %d bytes)' % (img.nbytes, stage.numel())
         stage[:img.nbytes].copy_(torch.from_numpy(img).reshape(-1))
-        return img.shape[0], img.shape[1]
+        return img.shape[0], img.shape[1], 'imread'
 
     def _take_slot(self):
         slot = self._free.popleft()
@@ -216,7 +229,13 @@ class ClipFeeder:
             from PIL import Image
             with Image.open(self.files[0]) as im:                                # header only: the frame size of the clip
                 w, h = im.size
-            self._slots(h * w * 3)
+            nbytes = h * w * 3
+            if str(self.files[0]).lower().endswith(('.jpg', '.jpeg')) and self.prep.device.type == 'cuda':
+                with open(self.files[0], 'rb') as f:                             # a JPEG's slot holds its coefficients + tables (4:4:4: 2x the frame)
+                    ji = jpeg_info(bytearray(f.read()))
+                if ji is not None:
+                    nbytes = max(nbytes, ji.coef_bytes + JPEG_QT_BYTES)
+            self._slots(nbytes)
         t_hi = min(t_hi, self._hi)
         while self._next < t_hi:
             t = self._next
@@ -273,16 +292,22 @@ class ClipFeeder:
             ent = (self._pool.submit(self._decode, self.files[t], slot), slot)
         fut, slot = ent
         c0 = time.perf_counter()
-        H, W = fut.result()
+        H, W, tag = fut.result()
         c1 = time.perf_counter()
         self.stats['wait_for_decode_s'] += c1 - c0
         self.decodes += 1
-        src = self._stage[slot][:H * W * 3].view(H, W, 3)
         dev = self.prep.device
+        jpeg = isinstance(tag, JpegInfo)
+        self.native_jpeg += jpeg
+        self.fallback_decodes += tag == 'imread'
+        # a JPEG's slot holds coefficients + tables (for 4:2:0 the size of the BGR frame): uploaded as they are, the frame is rebuilt there
+        src = self._stage[slot][:tag.coef_bytes + JPEG_QT_BYTES] if jpeg else self._stage[slot][:H * W * 3].view(H, W, 3)
         if dev.type == 'cuda':
             d = src.to(dev, non_blocking=True)
             ev = torch.cuda.Event(); ev.record()
             self._events[slot] = ev
+            if jpeg:
+                d = jpeg_reconstruct(d, tag)
         else:
             d = src.numpy().copy()                 # host stand-in (tests): own copy, the slot goes back to the ring
         out, img_shape, pad_shape, sf = self.prep.prep(d)
@@ -302,6 +327,63 @@ class ClipFeeder:
             fut.cancel()
         self._pool.shutdown(wait=True)
         self._pending = {}
+
+
+JPEG_QT_BYTES = 3 * 64 * 2         # the three quantisation tables (uint16, natural order) travel behind the coefficients
+
+
+class JpegInfo:
+    """what `vps_jpeg_info` reports about a file the native JPEG path takes (include/vps_hip.h)"""
+    __slots__ = ('H', 'W', 'ncomp', 'samp', 'grid', 'qt', 'coef_bytes')
+
+
+def jpeg_info(data, nbytes=None):
+    """geometry of a baseline JPEG (bytes-like, or a ctypes buffer + its length) -> JpegInfo; None for every file the native path
+    refuses (progressive, CMYK, unusual sampling, EXIF-rotated, truncated ..: the caller uses `imread`)"""
+    lib = hip.load_host()
+    if nbytes is None:
+        nbytes = len(data)
+        data = (ctypes.c_char * nbytes).from_buffer(data) if isinstance(data, (bytearray, memoryview)) else (ctypes.c_char * nbytes).from_buffer_copy(data)
+    ji = JpegInfo()
+    H, W, C, nb = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+    ji.samp, ji.grid = (ctypes.c_int32 * 6)(), (ctypes.c_int32 * 6)()
+    ji.qt = np.zeros((3, 64), dtype=np.uint16)
+    if lib.vps_jpeg_info(data, nbytes, ctypes.byref(H), ctypes.byref(W), ctypes.byref(C), ji.samp, ji.grid, ji.qt.ctypes.data_as(ctypes.c_void_p),
+                         ctypes.byref(nb)) != 0:
+        return None
+    ji.H, ji.W, ji.ncomp, ji.coef_bytes = H.value, W.value, C.value, nb.value
+    return ji
+
+
+def jpeg_reconstruct(buf, ji, ws=None):
+    """device uint8 buffer holding a JPEG's coefficients followed by its quantisation tables (`vps_jpeg_decode_coef` output +
+    JPEG_QT_BYTES) -> device BGR uint8 [H,W,3]: dequantisation, inverse DCT, chroma upsampling and colour conversion on the current
+    stream (csrc/jpeg_ops.hip), bit-exact with libjpeg's default decode. `ws`: reusable device workspace of coef_bytes / 2 bytes."""
+    if ws is None or ws.numel() < ji.coef_bytes // 2:
+        ws = torch.empty(ji.coef_bytes // 2, dtype=torch.uint8, device=buf.device)
+    out = torch.empty(ji.H, ji.W, 3, dtype=torch.uint8, device=buf.device)
+    hip.check(hip.load().vps_jpeg_reconstruct(hip.ptr(buf), ctypes.c_void_p(buf.data_ptr() + ji.coef_bytes), ji.H, ji.W, ji.ncomp, ji.samp, ji.grid,
+                                              hip.ptr(ws), ws.numel(), hip.ptr(out), hip.stream_ptr()), 'vps_jpeg_reconstruct')
+    return out
+
+
+def jpeg_decode(data, device='cuda'):
+    """bytes of a baseline JPEG -> device BGR uint8 [H,W,3], the pixels cv2.imread / PIL give (the JPEG counterpart of `png_decode`):
+    Huffman decode on the host (csrc/jpeg_host.cpp, no interpreter lock), one upload of the coefficients, reconstruction on the
+    device; None for a file the native path does not take"""
+    lib = hip.load_host()
+    data = data if isinstance(data, (bytearray, memoryview)) else bytearray(data)
+    cbuf = (ctypes.c_char * len(data)).from_buffer(data)
+    ji = jpeg_info(cbuf, len(data))
+    if ji is None:
+        return None
+    device = torch.device(device)
+    host = torch.empty(ji.coef_bytes + JPEG_QT_BYTES, dtype=torch.uint8)
+    if device.type == 'cuda':
+        host = host.pin_memory()
+    hip.check(lib.vps_jpeg_decode_coef(cbuf, len(data), ctypes.c_void_p(host.data_ptr()), ji.coef_bytes), 'vps_jpeg_decode_coef')
+    host[ji.coef_bytes:].copy_(torch.from_numpy(ji.qt.view(np.uint8).reshape(-1)))
+    return jpeg_reconstruct(host.to(device), ji)
 
 
 def png_decode(data):
