@@ -3,6 +3,7 @@
 // anonymous namespace: each translation unit gets its own copy.
 #pragma once
 #include "common.h"
+#include "conv_plan.h"
 #include <type_traits>
 #include <cstdlib>
 
@@ -15,6 +16,16 @@ namespace {
 constexpr int BM = 128;
 constexpr int BK = 32;
 constexpr int LDS_LD = 36;  // floats per LDS row (32 + 4 pad): 16B aligned, conflict-free b128 reads
+
+// host side: the runtime split-operand mode `prec` as a compile-time constant, f(std::integral_constant<int, VPS_PREC_...>). X6 = false:
+// the kernel has instances for the modes with two activation planes only (the planner sends it nothing else)
+template <bool X6, typename F>
+void with_prec(const int prec, F&& f) {
+    if (prec == VPS_PREC_BF16) f(std::integral_constant<int, VPS_PREC_BF16>{});
+    else if (prec == VPS_PREC_BF16X3) f(std::integral_constant<int, VPS_PREC_BF16X3>{});
+    else if (X6 && prec == VPS_PREC_BF16X6) f(std::integral_constant<int, X6 ? VPS_PREC_BF16X6 : VPS_PREC_F16X3>{});
+    else f(std::integral_constant<int, VPS_PREC_F16X3>{});
+}
 
 struct RowInfo {
     int iy0, ix0;   // top-left input coordinate of the receptive field (can be negative)

@@ -1,7 +1,7 @@
 // The 8-wave halo-staged convolution kernels ("h8": stride-1 3x3 / 2x2-class layers; "h8s2": stride-2 3x3 / 5x5 layers, phase-split) -
 // the largest items of the frame (FPN / TCEA / FlowNet 3x3 layers at 256x512 and 128x256, the FlowNet 5x5 stride-2 layers). Own
 // translation unit since round 6 (conv_mfma.hip takes minutes to compile); entered through vpsi_launch_conv_h8 / vpsi_launch_conv_h8s2
-// from launch_conv in conv_mfma.hip, which decides WHEN a layer comes here.
+// from vps_conv2d in conv_mfma.hip; conv_plan.cpp decides WHEN a layer comes here.
 #include "conv_common.h"
 
 namespace {
@@ -224,7 +224,7 @@ void conv_mfma_h8_kernel(const vps_conv_desc d, const int tiles_m, const int til
 
 // ================================================================================================
 // Stride-2 K x K layers (K = 3, 5) on the 8-wave halo structure ("h8s2"), phase-split staging. EXPERIMENTAL: dispatched only when
-// the environment variable VPS_S2_HALO is set (launch_conv); not part of the measured configuration of round 2.
+// the environment variable VPS_S2_HALO is set (conv_plan.cpp); not part of the measured configuration of round 2.
 // A stride-2 conv is four stride-1 convs on the (row, column)-parity sub-images of the input: tap (ky, kx) = (2j + a, 2i + b) of
 // output pixel (oy, ox) reads sub-image (a, b) at (oy + j, ox + i) (origin shifted by the padding). One stage of the k loop =
 // (32-channel chunk, phase (a, b)): the 8 x 32 output patch's sub-image patch ((8 + J_a - 1) x (32 + I_b - 1) pixels, J_0 = I_0 =
@@ -461,31 +461,25 @@ void conv_mfma_h8s2_kernel(const vps_conv_desc d, const int tiles_m, const int t
 
 }  // namespace
 
-int vpsi_launch_conv_h8p(const vps_conv_desc& d, int tiles_m8, int tiles_n, int chunks_per_split, long nblk8, hipStream_t s);
-
-// stride-1 K x K (K = 3, 2) layers with 128-column tiles: nblk8 blocks of 512 threads
+// stride-1 K x K (K = 3, 2) layers with 128-column tiles
 __attribute__((visibility("hidden")))
-void vpsi_launch_conv_h8(const vps_conv_desc& d, int tiles_m8, int tiles_n, int chunks_per_split, long nblk8, hipStream_t s) {
-    // f16x3: the pipelined instance (conv_h8p.hip, round 6)
-    if (vpsi_launch_conv_h8p(d, tiles_m8, tiles_n, chunks_per_split, nblk8, s)) return;
-#define VPS_H8_LAUNCH(MODE, K)                                                                                                   \
-    hipLaunchKernelGGL((conv_mfma_h8_kernel<MODE, K, K>), dim3((unsigned)nblk8), dim3(512), 0, s, d, tiles_m8, tiles_n, chunks_per_split)
-    if (d.prec == VPS_PREC_BF16) { if (d.KH == 3) VPS_H8_LAUNCH(VPS_PREC_BF16, 3); else VPS_H8_LAUNCH(VPS_PREC_BF16, 2); }
-    else if (d.prec == VPS_PREC_BF16X3) { if (d.KH == 3) VPS_H8_LAUNCH(VPS_PREC_BF16X3, 3); else VPS_H8_LAUNCH(VPS_PREC_BF16X3, 2); }
-    else { if (d.KH == 3) VPS_H8_LAUNCH(VPS_PREC_F16X3, 3); else VPS_H8_LAUNCH(VPS_PREC_F16X3, 2); }
-#undef VPS_H8_LAUNCH
+void vpsi_launch_conv_h8(const vps_conv_desc& d, const conv_plan& p, hipStream_t s) {
+    with_prec<false>(d.prec, [&](auto mode) {
+        constexpr int MODE = decltype(mode)::value;
+        if (d.KH == 3) hipLaunchKernelGGL((conv_mfma_h8_kernel<MODE, 3, 3>), dim3(p.grid), dim3(p.block), 0, s, d, p.tiles_m, p.tiles_n, p.chunks_per_split);
+        else hipLaunchKernelGGL((conv_mfma_h8_kernel<MODE, 2, 2>), dim3(p.grid), dim3(p.block), 0, s, d, p.tiles_m, p.tiles_n, p.chunks_per_split);
+    });
 }
 
 // stride-2 K x K (K = 3, 5) layers, 128- or 64-column tiles
 __attribute__((visibility("hidden")))
-void vpsi_launch_conv_h8s2(const vps_conv_desc& d, int tiles_m8, int tiles_n, int chunks_per_split, long nblk8, int bn, hipStream_t s) {
-#define VPS_H8S2_LAUNCH(MODE, K)                                                                                                 \
-    do {                                                                                                                         \
-        if (bn == 64) hipLaunchKernelGGL((conv_mfma_h8s2_kernel<MODE, K, 64>), dim3((unsigned)nblk8), dim3(512), 0, s, d, tiles_m8, tiles_n, chunks_per_split); \
-        else hipLaunchKernelGGL((conv_mfma_h8s2_kernel<MODE, K, 128>), dim3((unsigned)nblk8), dim3(512), 0, s, d, tiles_m8, tiles_n, chunks_per_split);         \
-    } while (0)
-    if (d.prec == VPS_PREC_BF16) { if (d.KH == 3) VPS_H8S2_LAUNCH(VPS_PREC_BF16, 3); else VPS_H8S2_LAUNCH(VPS_PREC_BF16, 5); }
-    else if (d.prec == VPS_PREC_BF16X3) { if (d.KH == 3) VPS_H8S2_LAUNCH(VPS_PREC_BF16X3, 3); else VPS_H8S2_LAUNCH(VPS_PREC_BF16X3, 5); }
-    else { if (d.KH == 3) VPS_H8S2_LAUNCH(VPS_PREC_F16X3, 3); else VPS_H8S2_LAUNCH(VPS_PREC_F16X3, 5); }
+void vpsi_launch_conv_h8s2(const vps_conv_desc& d, const conv_plan& p, hipStream_t s) {
+    with_prec<false>(d.prec, [&](auto mode) {
+        constexpr int MODE = decltype(mode)::value;
+#define VPS_H8S2_LAUNCH(K, BN) \
+    hipLaunchKernelGGL((conv_mfma_h8s2_kernel<MODE, K, BN>), dim3(p.grid), dim3(p.block), 0, s, d, p.tiles_m, p.tiles_n, p.chunks_per_split)
+        if (d.KH == 3) { if (d.tile_n == 64) VPS_H8S2_LAUNCH(3, 64); else VPS_H8S2_LAUNCH(3, 128); }
+        else { if (d.tile_n == 64) VPS_H8S2_LAUNCH(5, 64); else VPS_H8S2_LAUNCH(5, 128); }
 #undef VPS_H8S2_LAUNCH
+    });
 }

@@ -1,5 +1,5 @@
 // "h8p" (round 6): the 8-wave halo-staged stride-1 3x3 / 2x2 kernel of conv_h8.hip with every operand ONE STAGE FURTHER AHEAD.
-// Knock-outs of conv_mfma_h8_kernel on `256->256 3x3 @256x512` (tools/gpu_calls_r06/call_h8ko.sh): without the activation loads -14 %,
+// Knock-outs of conv_mfma_h8_kernel on `256->256 3x3 @256x512` (round 6): without the activation loads -14 %,
 // without the weight loads -17 %, without both and their staging -30 %, without the per-tap barrier only -4 % - and the bare core
 // (fragment reads + MFMAs) at 0.56 of the matrix pipe. The kernel was not short of bandwidth anywhere; each operand simply arrived late:
 //   * the weights of tap s+1 were requested at the start of tap s and waited for at its end (an L2 round trip per tap);
@@ -260,13 +260,8 @@ void conv_mfma_h8p_kernel(const vps_conv_desc d, const int tiles_m, const int ti
 
 }  // namespace
 
-// -> 1 if the pipelined instance takes this launch and was enqueued, 0: the caller launches conv_mfma_h8_kernel.
-// VPS_H8P=0 in the environment switches it off (A/B runs; read per call: tests compare the two kernels in one process)
+// f16x3 3x3 layers of the 8-wave halo family (VPS_H8P=0 in the environment: conv_mfma_h8_kernel, A/B runs)
 __attribute__((visibility("hidden")))
-int vpsi_launch_conv_h8p(const vps_conv_desc& d, int tiles_m8, int tiles_n, int chunks_per_split, long nblk8, hipStream_t s) {
-    const char* const e = getenv("VPS_H8P");
-    if (e && atoi(e) == 0) return 0;
-    if (d.prec != VPS_PREC_F16X3 || d.KH != 3) return 0;       // (the 2x2 instance - three chunks of 4 taps unrolled - spills: conv_mfma_h8_kernel keeps those layers)
-    hipLaunchKernelGGL((conv_mfma_h8p_kernel<VPS_PREC_F16X3, 3, 3>), dim3((unsigned)nblk8), dim3(512), 0, s, d, tiles_m8, tiles_n, chunks_per_split);
-    return 1;
+void vpsi_launch_conv_h8p(const vps_conv_desc& d, const conv_plan& p, hipStream_t s) {
+    hipLaunchKernelGGL((conv_mfma_h8p_kernel<VPS_PREC_F16X3, 3, 3>), dim3(p.grid), dim3(p.block), 0, s, d, p.tiles_m, p.tiles_n, p.chunks_per_split);
 }

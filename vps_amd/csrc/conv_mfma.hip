@@ -24,14 +24,6 @@
 //     the epilogue.
 #include "conv_common.h"
 
-int vpsi_launch_conv_q(const vps_conv_desc& d, int M, int tiles_m, int tiles_n, int per_split, long nblk, bool tapmajor, hipStream_t s);
-int vpsi_launch_conv_thin(const vps_conv_desc& d, hipStream_t s);
-void vpsi_launch_conv_small(const vps_conv_desc& d, int M, hipStream_t s);
-void vpsi_launch_conv_n16(const vps_conv_desc& d, long tiles2d8, hipStream_t s);
-void vpsi_launch_conv_h8(const vps_conv_desc& d, int tiles_m8, int tiles_n, int chunks_per_split, long nblk8, hipStream_t s);
-void vpsi_launch_conv_h8s2(const vps_conv_desc& d, int tiles_m8, int tiles_n, int chunks_per_split, long nblk8, int bn, hipStream_t s);
-
-
 namespace {
 template <int TM, int TN, int WAVES_M, int WAVES_N, bool DEFORM>
 __global__ __launch_bounds__(256, 2)
@@ -843,116 +835,71 @@ void conv_splitk_reduce_kernel(const vps_conv_desc d, const int M) {
     }
 }
 
+// the kernels of this file: 4-wave halo, exact fp32, pipelined split-operand. Wave arrangement <TM, TN, WAVES_M, WAVES_N> of the 4
+// waves of a block: weight fragments come from global memory (one 1 KB load per fragment = 64 cycles of the CU's vector-memory
+// pipe, tools/gapbench.hip), activation fragments from LDS (two conflict-free 1 KB reads per 32 cycles are free). Measured per layer
+// (profiles/r02_wave_arrangement_ab.txt): for 64-column tiles 2x2 waves of 64 rows x 32 columns beat 4x1 waves of 32 x 64 (half the
+// weight loads: +8..18 %); for 128-column tiles the 64 x 64 wave tile stays: 1x4 waves of 128 x 32 halve the weight loads again but
+// double the fragment reads of the halo tile, whose 18-row pitch costs a 2-way bank conflict (-7..13 %).
 template <int TM, int TN, int WAVES_M, int WAVES_N>
-int launch_conv(const vps_conv_desc& d, int M, hipStream_t s) {
-    constexpr int BN = WAVES_N * TN * 32;
-    const int tiles_m = cdiv(M, BM);
-    const int tiles_n = d.cout_pad / BN;
-    const int ksteps = d.kpad / BK;
-    // split-K: `ksplit` ranges of ceil(steps / ksplit) k-steps, the last one shorter when the division leaves a rest (every kernel clamps
-    // its range). Chunk-major layers (k = (32-channel chunk, tap)) are split over WHOLE chunks when ceil-division of the chunk count
-    // reproduces ksplit - the halo-staged kernels need that, and since round 6 the ranges may be uneven: FlowNet's 1026- / 770- / 386-
-    // channel decoder layers have 33 / 25 / 13 chunks, no even split exists, and unsplit they filled half of the chip.
-    const int ntap_all = d.KH * d.KW;
-    const int nch = d.korder == 1 ? ksteps / ntap_all : 0;
-    const bool chunk_split = d.ksplit > 1 && d.korder == 1 && nch > 0 && cdiv(nch, cdiv(nch, d.ksplit)) == d.ksplit;
-    const int per_split = chunk_split ? cdiv(nch, d.ksplit) * ntap_all : cdiv(ksteps, d.ksplit);
-    const int nsplit_eff = cdiv(ksteps, per_split);
-    if (nsplit_eff != d.ksplit) return VPS_EARG(20);  // caller must pick ksplit | ceil-consistent
-    const long nblk = (long)tiles_m * tiles_n * d.nclass * d.ksplit;
-    if (nblk <= 0 || nblk > 0x7fffffffL) return VPS_EARG(21);
-    // stride-1 3x3 / 2x2-class layers on whole 8x16 output patches: halo-staged kernel
-    // (patches may overhang the right / bottom edge; used when that wastes less than a third of the computed rows)
-    const long tiles2d = (long)d.N * ((d.Qh + 7) / 8) * ((d.Qw + 15) / 16);
-    // split-K there is over whole 32-channel chunks: the k-steps of a split must be a whole number of chunks
-    const int ntap = d.KH * d.KW;
-    const bool halo = d.prec != VPS_PREC_F32 && !d.offset && d.stride == 1 && d.korder == 1 && d.KH == d.KW && (d.KH == 3 || d.KH == 2) &&
-                      tiles2d * 128 * 2 <= (long)M * 3 && (d.ksplit == 1 || chunk_split);
-    // 8-wave variant (256-row tiles, weights through LDS): 128-column layers in the modes whose two activation planes leave room
-    // for the weight buffers, when the 8 x 32 patches waste little and there are enough tiles to give every CU one
-    const long tiles2d8 = (long)d.N * ((d.Qh + 7) / 8) * ((d.Qw + 31) / 32);
-    // VPS_H8_MIN_CHUNKS=n: layers with fewer than n 32-channel chunks stay on the 4-wave halo kernel (two blocks per CU: one
-    // block's store drain overlaps the other's k loop; the 8-wave kernel holds a CU alone and its short-K tiles are mostly drain)
-    // round 5, measured: `64->128 3x3 @512x1024` 0.303 -> 0.264 ms on the 4-wave kernel, layers with >= 4 chunks unchanged -> 3
-    static const int h8_min_chunks = getenv("VPS_H8_MIN_CHUNKS") ? atoi(getenv("VPS_H8_MIN_CHUNKS")) : 3;
-    const bool h8 = halo && BN == 128 && (d.prec == VPS_PREC_F16X3 || d.prec == VPS_PREC_BF16X3 || d.prec == VPS_PREC_BF16) &&
-                    tiles2d8 * 256 * 2 <= (long)M * 3 && tiles2d8 * tiles_n * d.nclass * d.ksplit >= 256 && ksteps / ntap >= h8_min_chunks;
-    // stride-2 3x3 / 5x5 layers on the phase-split 8-wave halo kernel (VPS_S2_HALO=0 in the environment switches it off: A/B runs)
-    static const bool s2_enabled = !(getenv("VPS_S2_HALO") && getenv("VPS_S2_HALO")[0] == '0');
-    const bool h8s2 = s2_enabled && (BN == 128 || BN == 64) && (d.prec == VPS_PREC_F16X3 || d.prec == VPS_PREC_BF16X3 || d.prec == VPS_PREC_BF16) && !d.offset &&
-                      d.stride == 2 && d.nclass == 1 && d.korder == 1 && d.KH == d.KW && (d.KH == 3 || d.KH == 5) &&
-                      d.pad_y[0] == d.KH / 2 && d.pad_x[0] == d.KW / 2 && tiles2d8 * 256 * 2 <= (long)M * 3 &&
-                      tiles2d8 * tiles_n * d.ksplit >= 256 && (d.ksplit == 1 || chunk_split);
-    // 5..16 output channels, stride-1 3x3 / 2x2-class layers with enough 8 x 32 patches: the 16x16x32 kernel (VPS_N16=0 switches it off)
-    static const bool n16_enabled = !(getenv("VPS_N16") && getenv("VPS_N16")[0] == '0');
-    // VPS_N32=0: layers with 17 .. 32 output channels stay on the 32-column halo kernel (A/B; the two-column-block instance is round 6's)
-    const char* const n32_env = getenv("VPS_N32");
-    const int n16_max_cout = (n32_env && n32_env[0] == '0') ? 16 : 32;
-    const bool n16 = n16_enabled && BN == 32 && d.prec == VPS_PREC_F16X3 && halo && d.cout > 4 && d.cout <= n16_max_cout && d.cout_pad == 32 && d.ksplit == 1 &&
-                     !d.gn_stats && tiles2d8 * 256 * 2 <= (long)M * 3 && tiles2d8 * d.nclass >= 256;
-    if (n16) {
-        vpsi_launch_conv_n16(d, tiles2d8, s);
-    } else if (h8s2) {
-        vpsi_launch_conv_h8s2(d, (int)tiles2d8, tiles_n, per_split / ntap, (long)tiles2d8 * tiles_n * d.ksplit, BN == 64 ? 64 : 128, s);
-    } else if (h8) {
-        vpsi_launch_conv_h8(d, (int)tiles2d8, tiles_n, per_split / ntap, (long)tiles2d8 * tiles_n * d.nclass * d.ksplit, s);
-    } else if (halo) {
-        const int tiles_m2 = (int)tiles2d;
-        const long nblk2 = (long)tiles_m2 * tiles_n * d.nclass * d.ksplit;
-        if (nblk2 > 0x7fffffffL) return VPS_EARG(21);
-#define VPS_HALO_LAUNCH(MODE, K)                                                                                                  \
-    hipLaunchKernelGGL((conv_mfma_bf16h_kernel<TM, TN, WAVES_M, WAVES_N, MODE, K, K>), dim3((unsigned)nblk2), dim3(256), 0, s, d, tiles_m2, \
-                       tiles_n, per_split / ntap)
-        if (d.prec == VPS_PREC_BF16) { if (d.KH == 3) VPS_HALO_LAUNCH(VPS_PREC_BF16, 3); else VPS_HALO_LAUNCH(VPS_PREC_BF16, 2); }
-        else if (d.prec == VPS_PREC_BF16X3) { if (d.KH == 3) VPS_HALO_LAUNCH(VPS_PREC_BF16X3, 3); else VPS_HALO_LAUNCH(VPS_PREC_BF16X3, 2); }
-        else if (d.prec == VPS_PREC_F16X3) { if (d.KH == 3) VPS_HALO_LAUNCH(VPS_PREC_F16X3, 3); else VPS_HALO_LAUNCH(VPS_PREC_F16X3, 2); }
-        else { if (d.KH == 3) VPS_HALO_LAUNCH(VPS_PREC_BF16X6, 3); else VPS_HALO_LAUNCH(VPS_PREC_BF16X6, 2); }
-#undef VPS_HALO_LAUNCH
-    } else {
-    // deformable layers: the pipelined kernel when the k order is chunk-major (every layer of the path; weights in fragment order),
-    // the two-barrier kernel for the tap-major order (row-major weights: vps_hip.h)
-    const bool dcn_pipe = true;                            // (tap-major deformable launches are refused by vps_conv2d)
-    const bool tapmajor = d.korder == 0 && ntap > 1;      // small channel counts; a 1x1 layer is the one-tap case of the chunk-major order
-#define VPS_CONV_LAUNCH(KERNEL)                                                                              \
-    hipLaunchKernelGGL((KERNEL), dim3((unsigned)nblk), dim3(256), 0, s, d, M, tiles_m, tiles_n, per_split)
-    // uniform-lead kernel (conv_q.hip: both operands two k-steps ahead, weights through LDS): every non-deformable layer of the
-    // modes with two activation planes on 64- / 128-column tiles. VPS_UNIFORM_LEAD=0 in the environment switches back to the
-    // pipelined kernel (A/B runs): bit 0 = chunk-major layers, bit 1 = tap-major layers.
-    const bool q_done = BN >= 64 && vpsi_launch_conv_q(d, M, tiles_m, tiles_n, per_split, nblk, tapmajor, s);
-    if (q_done) {
-    } else if (d.prec == VPS_PREC_F32) {
+void launch_conv(const vps_conv_desc& d, const conv_plan& p, hipStream_t s) {
+    const dim3 grid(p.grid), block(p.block);
+    if (p.kernel == CONV_K_HALO) {
+        with_prec<true>(d.prec, [&](auto mode) {
+            constexpr int MODE = decltype(mode)::value;
+            if (d.KH == 3) hipLaunchKernelGGL((conv_mfma_bf16h_kernel<TM, TN, WAVES_M, WAVES_N, MODE, 3, 3>), grid, block, 0, s, d, p.tiles_m, p.tiles_n, p.chunks_per_split);
+            else hipLaunchKernelGGL((conv_mfma_bf16h_kernel<TM, TN, WAVES_M, WAVES_N, MODE, 2, 2>), grid, block, 0, s, d, p.tiles_m, p.tiles_n, p.chunks_per_split);
+        });
+        return;
+    }
+#define VPS_CONV_LAUNCH(KERNEL) hipLaunchKernelGGL((KERNEL), grid, block, 0, s, d, p.M, p.tiles_m, p.tiles_n, p.per_split)
+    if (p.kernel == CONV_K_F32) {
         if (d.offset) VPS_CONV_LAUNCH((conv_mfma_f32_kernel<TM, TN, WAVES_M, WAVES_N, true>));
         else VPS_CONV_LAUNCH((conv_mfma_f32_kernel<TM, TN, WAVES_M, WAVES_N, false>));
-    } else if (d.prec == VPS_PREC_BF16) {
-        if (d.offset && dcn_pipe) VPS_CONV_LAUNCH((conv_mfma_bf16p_kernel<TM, TN, WAVES_M, WAVES_N, VPS_PREC_BF16, false, true>));
-        else if (tapmajor) VPS_CONV_LAUNCH((conv_mfma_bf16p_kernel<TM, TN, WAVES_M, WAVES_N, VPS_PREC_BF16, true>));
-        else VPS_CONV_LAUNCH((conv_mfma_bf16p_kernel<TM, TN, WAVES_M, WAVES_N, VPS_PREC_BF16, false>));
-    } else if (d.prec == VPS_PREC_BF16X3) {
-        if (d.offset && dcn_pipe) VPS_CONV_LAUNCH((conv_mfma_bf16p_kernel<TM, TN, WAVES_M, WAVES_N, VPS_PREC_BF16X3, false, true>));
-        else if (tapmajor) VPS_CONV_LAUNCH((conv_mfma_bf16p_kernel<TM, TN, WAVES_M, WAVES_N, VPS_PREC_BF16X3, true>));
-        else VPS_CONV_LAUNCH((conv_mfma_bf16p_kernel<TM, TN, WAVES_M, WAVES_N, VPS_PREC_BF16X3, false>));
-    } else if (d.prec == VPS_PREC_F16X3) {
-        if (d.offset && dcn_pipe) VPS_CONV_LAUNCH((conv_mfma_bf16p_kernel<TM, TN, WAVES_M, WAVES_N, VPS_PREC_F16X3, false, true>));
-        else if (tapmajor) VPS_CONV_LAUNCH((conv_mfma_bf16p_kernel<TM, TN, WAVES_M, WAVES_N, VPS_PREC_F16X3, true>));
-        else VPS_CONV_LAUNCH((conv_mfma_bf16p_kernel<TM, TN, WAVES_M, WAVES_N, VPS_PREC_F16X3, false>));
-    } else {
-        if (d.offset && dcn_pipe) VPS_CONV_LAUNCH((conv_mfma_bf16p_kernel<TM, TN, WAVES_M, WAVES_N, VPS_PREC_BF16X6, false, true>));
-        else if (tapmajor) VPS_CONV_LAUNCH((conv_mfma_bf16p_kernel<TM, TN, WAVES_M, WAVES_N, VPS_PREC_BF16X6, true>));
-        else VPS_CONV_LAUNCH((conv_mfma_bf16p_kernel<TM, TN, WAVES_M, WAVES_N, VPS_PREC_BF16X6, false>));
+        return;
     }
+    // deformable layers: the chunk-major k order (weights in fragment order); tap-major: small channel counts - a 1x1 layer is the
+    // one-tap case of the chunk-major order
+    const bool tapmajor = d.korder == 0 && d.KH * d.KW > 1;
+    with_prec<true>(d.prec, [&](auto mode) {
+        constexpr int MODE = decltype(mode)::value;
+        if (d.offset) VPS_CONV_LAUNCH((conv_mfma_bf16p_kernel<TM, TN, WAVES_M, WAVES_N, MODE, false, true>));
+        else if (tapmajor) VPS_CONV_LAUNCH((conv_mfma_bf16p_kernel<TM, TN, WAVES_M, WAVES_N, MODE, true>));
+        else VPS_CONV_LAUNCH((conv_mfma_bf16p_kernel<TM, TN, WAVES_M, WAVES_N, MODE, false>));
+    });
 #undef VPS_CONV_LAUNCH
-    }
-    int st = vps_launch_status();
-    if (st) return st;
-    if (d.ksplit > 1 && !d.tile_counter) {
-        const size_t total = (size_t)d.nclass * M * d.cout;
-        const bool vec = !((d.cout | d.cout_pad | d.out_ld | d.out_coff) & 3) && !((uintptr_t)d.out & 15) &&
-                         (!d.res || (!((d.res_ld | d.res_coff) & 3) && !((uintptr_t)d.res & 15)));
-        if (vec) hipLaunchKernelGGL(conv_splitk_reduce_kernel<4>, dim3(stream_grid((long)(total / 4), 256)), dim3(256), 0, s, d, M);
-        else hipLaunchKernelGGL(conv_splitk_reduce_kernel<1>, dim3(stream_grid((long)total, 256)), dim3(256), 0, s, d, M);
-        st = vps_launch_status();
-    }
-    return st;
+}
+
+// the environment switches of the conv family (A/B runs): VPS_x=0 switches x off. Cached at the first call, except the four that tests
+// flip inside one process: those are read per call, and only for a descriptor they can matter to (the planner holds the whole
+// condition) - a cached descriptor costs one vps_conv2d call per layer per frame, and at most one of the four applies to a layer.
+conv_switches conv_switches_now(const vps_conv_desc& d) {
+    const auto on = [](const char* name) { const char* const e = getenv(name); return !(e && atoi(e) == 0); };
+    const auto not0 = [](const char* name) { const char* const e = getenv(name); return !(e && e[0] == '0'); };
+    static const bool s2_halo = not0("VPS_S2_HALO"), thin = on("VPS_THIN"), debug_occ = getenv("VPS_DEBUG_OCC") != nullptr;
+    conv_switches sw = {true, true, true, true, s2_halo, thin, debug_occ};
+    if (d.prec != VPS_PREC_F16X3) return sw;
+    if (d.tile_n == 32) {
+        if (d.cout > 16) sw.n32 = not0("VPS_N32");
+        else if (d.nclass == 4) sw.n16t = on("VPS_N16T");
+    } else if (d.tile_n <= 128 && d.KH == 1) sw.pw = on("VPS_PW");
+    else if (d.tile_n == 128 && d.KH == 3 && d.stride == 1) sw.h8p = on("VPS_H8P");
+    return sw;
+}
+
+// the device numbers of the planner, once: occupancy of the persistent kernels x compute units
+const conv_limits& conv_limits_once(const bool debug) {
+    static const conv_limits lim = [debug] {
+        conv_limits l = {};
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&l.cus, hipDeviceAttributeMultiprocessorCount, dev);
+        vpsi_conv_pw_limits(l, debug);
+        vpsi_conv_thin_limits(l, debug);
+        if (debug) vpsi_conv_q_debug_occ();
+        return l;
+    }();
+    return lim;
 }
 
 }  // namespace
@@ -960,62 +907,32 @@ int launch_conv(const vps_conv_desc& d, int M, hipStream_t s) {
 extern "C" int vps_conv2d(const vps_conv_desc* dp, void* stream) {
     if (!dp) return VPS_EARG(1);
     const vps_conv_desc& d = *dp;
-    if (!d.in || !d.out) return VPS_EARG(2);
-    if (d.prec < VPS_PREC_F32 || d.prec > VPS_PREC_F16X3) return VPS_EARG(12);
-    if (d.prec == VPS_PREC_F32 ? !d.w : !d.w_split) return VPS_EARG(13);
-    if ((d.in_ld & 3) || (d.in_coff & 3) || (d.cin_pad & 3) || d.cin_pad <= 0) return VPS_EARG(3);
-    if ((d.kpad % BK) || d.kpad < d.KH * d.KW * d.cin_pad || (d.korder != 0 && d.korder != 1)) return VPS_EARG(4);
-    if (d.korder == 1 && d.kpad != d.KH * d.KW * ((d.cin_pad + BK - 1) / BK) * BK) return VPS_EARG(14);
-    if (d.tile_n != 32 && d.tile_n != 64 && d.tile_n != 128 && !(d.tile_n == 256 && d.offset && d.prec == VPS_PREC_F16X3 && d.korder == 1)) return VPS_EARG(5);
-    if (d.cout_pad % d.tile_n || d.cout > d.cout_pad || d.cout <= 0) return VPS_EARG(6);
-    if (d.nclass != d.os_y * d.os_x || d.nclass < 1 || d.os_y > 2 || d.os_x > 2) return VPS_EARG(7);
-    if (d.ksplit < 1 || (d.ksplit > 1 && !d.ws)) return VPS_EARG(8);
-    if (d.offset && (d.nclass != 1 || d.off_ld < 2 * d.KH * d.KW || d.KH * d.KW > 9 || d.H > 65535 || d.W > 65535)) return VPS_EARG(9);
-    // deformable layers of the split-operand modes: chunk-major k order only (every layer of the path; the tap-major two-barrier kernel of
-    // rounds 1-2 is gone) - a tap-major deformable layer runs in VPS_PREC_F32 (vps_amd/nhwc.py packs it that way)
-    if (d.offset && d.prec != VPS_PREC_F32 && d.korder != 1) return VPS_EARG(17);
-    if (((uintptr_t)d.in & 15) || ((uintptr_t)d.w & 15) || ((uintptr_t)d.w_split & 15)) return VPS_EARG(10);
-    // the split-operand kernels address the input and the weights through 32-bit buffer offsets
-    if (d.prec != VPS_PREC_F32 && (size_t)d.N * d.H * d.W * d.in_ld * sizeof(float) >= 0xFFFFFFF0ull) return VPS_EARG(16);
-    // GroupNorm sums in the epilogue: the deformable kernel of the split-operand modes only, unsplit, float4 stores, groups of 4 | 8 | 16 ...
-    if (d.gn_stats && (!d.offset || d.prec == VPS_PREC_F32 || d.ksplit != 1 || d.gn_rep < 1 || (d.gn_rep & (d.gn_rep - 1)) || (d.gn_cpg != 4 && (d.gn_cpg < 8 || (d.gn_cpg & 7))) || d.cout % d.gn_cpg ||
-                       ((d.cout | d.out_ld | d.out_coff) & 3) || ((uintptr_t)d.out & 15) || d.res || ((uintptr_t)d.gn_stats & 7)))
-        return VPS_EARG(15);
-    const long Ml = (long)d.N * d.Qh * d.Qw;
-    if (Ml <= 0 || Ml > 0x7fffffffL) return VPS_EARG(11);
-    const int M = (int)Ml;
+    if (const int e = vpsi_conv_check(d)) return e;               // before the device is touched
+    const conv_switches sw = conv_switches_now(d);
+    const conv_plan p = vpsi_conv_plan(d, conv_limits_once(sw.debug_occ), sw);
     hipStream_t s = (hipStream_t)stream;
-    // narrow outputs (cout <= 4) in exact fp32 on the vector ALU: conv_small.hip
-    if (d.cout <= 4 && d.prec == VPS_PREC_F32 && !d.offset && d.ksplit == 1 && d.tile_n == 32) {
-        vpsi_launch_conv_small(d, M, s);
-        return vps_launch_status();
+    switch (p.kernel) {
+        case CONV_K_NONE: return p.err;
+        case CONV_K_SMALL3X3V: case CONV_K_SMALL_BATCHED: case CONV_K_SMALL: vpsi_launch_conv_small(d, p, s); break;
+        case CONV_K_THIN: vpsi_launch_conv_thin(d, p, s); break;
+        case CONV_K_DCN256:
+            hipLaunchKernelGGL((conv_mfma_bf16p_kernel<2, 4, 2, 2, VPS_PREC_F16X3, false, true>), dim3(p.grid), dim3(p.block), 0, s, d, p.M, p.tiles_m, p.tiles_n, p.per_split);
+            break;
+        case CONV_K_N16T: case CONV_K_N32: case CONV_K_N16: vpsi_launch_conv_n16(d, p, s); break;
+        case CONV_K_H8S2: vpsi_launch_conv_h8s2(d, p, s); break;
+        case CONV_K_H8P: vpsi_launch_conv_h8p(d, p, s); break;
+        case CONV_K_H8: vpsi_launch_conv_h8(d, p, s); break;
+        case CONV_K_PW: vpsi_launch_conv_pw(d, p, s); break;
+        case CONV_K_Q: vpsi_launch_conv_q(d, p, s); break;
+        default:        // CONV_K_HALO, CONV_K_F32, CONV_K_BF16P
+            if (d.tile_n == 128) launch_conv<2, 2, 2, 2>(d, p, s);
+            else if (d.tile_n == 64) launch_conv<2, 1, 2, 2>(d, p, s);
+            else launch_conv<1, 1, 4, 1>(d, p, s);
     }
-    // thin-input layers at full resolution (3 / 6 / 11 / 12 -> 64 channels) with their own weight packing: conv_thin.hip
-    if (d.w_thin && vpsi_launch_conv_thin(d, s)) return vps_launch_status();
-    // wave arrangement <TM, TN, WAVES_M, WAVES_N> of the 4 waves of a block. Weight fragments come from global memory (one 1 KB
-    // load per fragment = 64 cycles of the CU's vector-memory pipe, tools/gapbench.hip), activation fragments from LDS (two
-    // conflict-free 1 KB reads per 32 cycles are free). Measured per layer (profiles/r02_wave_arrangement_ab.txt): for 64-column
-    // tiles 2x2 waves of 64 rows x 32 columns beat 4x1 waves of 32 x 64 (half the weight loads: +8..18 %); for 128-column tiles
-    // the 64 x 64 wave tile stays: 1x4 waves of 128 x 32 halve the weight loads again but double the fragment reads of the halo
-    // tile, whose 18-row pitch costs a 2-way bank conflict (-7..13 %).
-    if (d.tile_n == 256) {
-        // deformable layers with >= 256 output channels (round 5): ONE block computes all 256 columns of its 128 pixels - the bilinear
-        // loader (4 corner loads + 16 multiply-adds + the fp16 split per staged float4: 8.3 VALU per MFMA with 128 columns) runs once
-        // instead of twice. 2 x 2 waves of 64 x 128, accumulators in AGPRs, one block per CU.
-        const int tiles_m = cdiv(M, BM), tiles_n = d.cout_pad / 256, ksteps = d.kpad / BK;
-        const int per_split = cdiv(ksteps, d.ksplit);
-        if (cdiv(ksteps, per_split) != d.ksplit) return VPS_EARG(20);
-        const long nblk = (long)tiles_m * tiles_n * d.ksplit;
-        hipLaunchKernelGGL((conv_mfma_bf16p_kernel<2, 4, 2, 2, VPS_PREC_F16X3, false, true>), dim3((unsigned)nblk), dim3(256), 0, s, d, M, tiles_m, tiles_n, per_split);
-        int st = vps_launch_status();
-        if (st || d.ksplit == 1 || d.tile_counter) return st;
-        const size_t total = (size_t)M * d.cout;
-        hipLaunchKernelGGL(conv_splitk_reduce_kernel<4>, dim3(stream_grid((long)(total / 4), 256)), dim3(256), 0, s, d, M);
-        return vps_launch_status();
-    }
-    switch (d.tile_n) {
-        case 128: return launch_conv<2, 2, 2, 2>(d, M, s);
-        case 64: return launch_conv<2, 1, 2, 2>(d, M, s);
-        default: return launch_conv<1, 1, 4, 1>(d, M, s);
-    }
+    int st = vps_launch_status();
+    if (st || !p.needs_reduce) return st;
+    const size_t total = (size_t)d.nclass * p.M * d.cout;
+    if (p.reduce_v4) hipLaunchKernelGGL(conv_splitk_reduce_kernel<4>, dim3(stream_grid((long)(total / 4), 256)), dim3(256), 0, s, d, p.M);
+    else hipLaunchKernelGGL(conv_splitk_reduce_kernel<1>, dim3(stream_grid((long)total, 256)), dim3(256), 0, s, d, p.M);
+    return vps_launch_status();
 }

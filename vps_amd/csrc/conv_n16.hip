@@ -1,5 +1,5 @@
 // The 16-column kernels of vps_conv2d (narrow-output layers at full resolution: the FlowNetFusion / FlowNetSD decoder). Own translation
-// unit since round 6; entered through vpsi_launch_conv_n16 from launch_conv (conv_mfma.hip), which decides WHEN a layer comes here.
+// unit since round 6; entered through vpsi_launch_conv_n16 from vps_conv2d (conv_mfma.hip); conv_plan.cpp decides WHEN a layer comes here.
 #include "conv_common.h"
 
 namespace {
@@ -593,24 +593,16 @@ void conv_mfma_n32_kernel(const vps_conv_desc d, const int tiles_m) {
 
 }  // namespace
 
-// 5..16 output channels, stride-1 3x3 / 2x2-class layers with enough 8 x 32 patches (launch_conv decides). VPS_N16T=0 switches the
-// class-fused instance for transposed layers off (A/B; read per call)
+// n16t: the four classes of a transposed layer in one block; n32: 17 .. 32 output channels, two column blocks per wave; n16: 5 .. 16
 __attribute__((visibility("hidden")))
-void vpsi_launch_conv_n16(const vps_conv_desc& d, long tiles2d8, hipStream_t s) {
-    const char* const e = getenv("VPS_N16T");
-    const bool fused = !(e && atoi(e) == 0) && d.KH == 2 && d.KW == 2 && d.nclass == 4 && d.os_y == 2 && d.os_x == 2 &&
-                       d.pad_y[0] >= 0 && d.pad_y[0] <= 1 && d.pad_y[1] >= 0 && d.pad_y[1] <= 1 &&
-                       d.pad_x[0] >= 0 && d.pad_x[0] <= 1 && d.pad_x[1] >= 0 && d.pad_x[1] <= 1;
-    if (fused && d.cout <= 16) {
-        hipLaunchKernelGGL((conv_mfma_n16t_kernel<VPS_PREC_F16X3>), dim3((unsigned)tiles2d8), dim3(512), 0, s, d, (int)tiles2d8);
-        return;
+void vpsi_launch_conv_n16(const vps_conv_desc& d, const conv_plan& p, hipStream_t s) {
+    const dim3 grid(p.grid), block(p.block);
+    if (p.kernel == CONV_K_N16T) hipLaunchKernelGGL((conv_mfma_n16t_kernel<VPS_PREC_F16X3>), grid, block, 0, s, d, p.tiles_m);
+    else if (p.kernel == CONV_K_N32) {
+        if (d.KH == 3) hipLaunchKernelGGL((conv_mfma_n32_kernel<VPS_PREC_F16X3, 3, 3>), grid, block, 0, s, d, p.tiles_m);
+        else hipLaunchKernelGGL((conv_mfma_n32_kernel<VPS_PREC_F16X3, 2, 2>), grid, block, 0, s, d, p.tiles_m);
+    } else {
+        if (d.KH == 3) hipLaunchKernelGGL((conv_mfma_n16_kernel<VPS_PREC_F16X3, 3, 3>), grid, block, 0, s, d, p.tiles_m);
+        else hipLaunchKernelGGL((conv_mfma_n16_kernel<VPS_PREC_F16X3, 2, 2>), grid, block, 0, s, d, p.tiles_m);
     }
-    const long nblk8 = tiles2d8 * d.nclass;
-    if (d.cout > 16) {                                   // 17 .. 32 output channels: two column blocks per wave
-        if (d.KH == 3) hipLaunchKernelGGL((conv_mfma_n32_kernel<VPS_PREC_F16X3, 3, 3>), dim3((unsigned)nblk8), dim3(512), 0, s, d, (int)tiles2d8);
-        else hipLaunchKernelGGL((conv_mfma_n32_kernel<VPS_PREC_F16X3, 2, 2>), dim3((unsigned)nblk8), dim3(512), 0, s, d, (int)tiles2d8);
-        return;
-    }
-    if (d.KH == 3) hipLaunchKernelGGL((conv_mfma_n16_kernel<VPS_PREC_F16X3, 3, 3>), dim3((unsigned)nblk8), dim3(512), 0, s, d, (int)tiles2d8);
-    else hipLaunchKernelGGL((conv_mfma_n16_kernel<VPS_PREC_F16X3, 2, 2>), dim3((unsigned)nblk8), dim3(512), 0, s, d, (int)tiles2d8);
 }

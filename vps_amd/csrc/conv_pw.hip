@@ -385,64 +385,29 @@ void conv_pw_kernel(const vps_conv_desc d, const int M, const int tiles_m, const
     report_range<PMODE>(d, amax);
 }
 
-int pw_resident(int tn) {
-    static int res[2] = {0, 0};
-    int& r = res[tn == 2 ? 1 : 0];
-    if (!r) {
-        int per_cu = 0, dev = 0, cus = 256;
-        if (tn == 2) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv_pw_kernel<2, false, 0>, 256, 0);
-        else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv_pw_kernel<1, false, 0>, 256, 0);
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        r = (per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 256);
-        if (getenv("VPS_DEBUG_OCC")) fprintf(stderr, "[vps] pointwise kernel <TN %d>: %d blocks/CU\n", tn, per_cu);
-    }
-    return r;
-}
-
 }  // namespace
 
-// -> 1 if the persistent pointwise kernel takes this launch and was enqueued, 0 if the caller has to use another kernel.
-// VPS_PW=0 in the environment switches the family off (A/B runs); VPS_PW_MIN_ROUNDS=r: layers with fewer than r rounds of resident
-// blocks stay on the uniform-lead kernel (persistence pays from the second tile of a block on).
 __attribute__((visibility("hidden")))
-int vpsi_launch_conv_pw(const vps_conv_desc& d, int M, int tiles_m, int tiles_n, hipStream_t s) {
-    const char* const on_env = getenv("VPS_PW");                 // read per call: tests switch it inside one process
-    const int on = on_env ? atoi(on_env) : 1;
-    static const int min_rounds = getenv("VPS_PW_MIN_ROUNDS") ? atoi(getenv("VPS_PW_MIN_ROUNDS")) : 2;
-    if (!on || d.prec != VPS_PREC_F16X3 || d.offset || d.KH != 1 || d.KW != 1 || d.nclass != 1 || d.ksplit != 1 || d.gn_stats) return 0;
-    if (d.pad_y[0] || d.pad_x[0] || (d.cin_pad & 31) || d.kpad != d.cin_pad || (d.tile_n != 128 && d.tile_n != 64)) return 0;
-    const int nk = d.kpad / BK;
-    if (nk < 2 || (nk & 1)) return 0;
-    if (d.Ho != d.Qh || d.Wo != d.Qw || (d.stride == 1 && (d.H != d.Qh || d.W != d.Qw))) return 0;
-    // float4 buffer stores / residual loads: 16-byte aligned channel windows of tensors below 4 GiB
-    if (((d.cout | d.out_ld | d.out_coff) & 3) || ((uintptr_t)d.out & 15) || (size_t)d.N * d.Ho * d.Wo * d.out_ld * sizeof(float) >= 0xFFFFFE00ull) return 0;
-    if (d.res && (((d.res_ld | d.res_coff) & 3) || ((uintptr_t)d.res & 15) || d.res_shift < 0 || d.res_shift > 4 ||
-                  (size_t)d.N * (d.Ho >> d.res_shift) * (d.Wo >> d.res_shift) * d.res_ld * sizeof(float) >= 0xFFFFFE00ull)) return 0;
-    if ((size_t)d.N * d.H * d.W * d.in_ld * sizeof(float) >= 0xFFFFFE00ull) return 0;
+void vpsi_conv_pw_limits(conv_limits& lim, bool debug) {
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&lim.pw_per_cu[0], conv_pw_kernel<1, false, 0>, 256, 0);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&lim.pw_per_cu[1], conv_pw_kernel<2, false, 0>, 256, 0);
+    if (debug) for (int tn = 1; tn <= 2; ++tn) fprintf(stderr, "[vps] pointwise kernel <TN %d>: %d blocks/CU\n", tn, lim.pw_per_cu[tn - 1]);
+}
+
+// f16x3 1x1 layers with at least two rounds of resident blocks (VPS_PW=0 in the environment switches the family off: A/B runs)
+__attribute__((visibility("hidden")))
+void vpsi_launch_conv_pw(const vps_conv_desc& d, const conv_plan& p, hipStream_t s) {
     const int tn = d.tile_n == 128 ? 2 : 1;
-    const int resident = pw_resident(tn);
-    const long total = (long)tiles_m * tiles_n;
-    const int unit = 8 * tiles_n;                              // a grid is whole groups of (8 XCDs x the column tiles)
-    if (resident < unit || total < (long)min_rounds * resident) return 0;
-    // whole rounds: every block walks the same number of tiles
-    const long rounds = (total + resident - 1) / resident;
-    long grid = (total + rounds - 1) / rounds;
-    grid = (grid + unit - 1) / unit * unit;
-    if (grid > resident) grid = resident / unit * unit;
-    const int mper = (int)(grid / unit);
-    const int nit = (tiles_m + mper * 8 - 1) / (mper * 8);
-#define VPS_PW_LAUNCH(TNV, RESV, NKV) hipLaunchKernelGGL((conv_pw_kernel<TNV, RESV, NKV>), dim3((unsigned)grid), dim3(256), 0, s, d, M, tiles_m, tiles_n, nk, nit)
+#define VPS_PW_LAUNCH(TNV, RESV, NKV) hipLaunchKernelGGL((conv_pw_kernel<TNV, RESV, NKV>), dim3(p.grid), dim3(p.block), 0, s, d, p.M, p.tiles_m, p.tiles_n, p.nk, p.nit)
 #define VPS_PW_NK(TNV, RESV)                                         \
     do {                                                             \
-        if (nk == 2) VPS_PW_LAUNCH(TNV, RESV, 2);                    \
-        else if (nk == 4) VPS_PW_LAUNCH(TNV, RESV, 4);               \
-        else if (nk == 8) VPS_PW_LAUNCH(TNV, RESV, 8);               \
+        if (p.nk == 2) VPS_PW_LAUNCH(TNV, RESV, 2);                  \
+        else if (p.nk == 4) VPS_PW_LAUNCH(TNV, RESV, 4);             \
+        else if (p.nk == 8) VPS_PW_LAUNCH(TNV, RESV, 8);             \
         else VPS_PW_LAUNCH(TNV, RESV, 0);                            \
     } while (0)
     if (d.res) { if (tn == 2) VPS_PW_NK(2, true); else VPS_PW_NK(1, true); }
     else { if (tn == 2) VPS_PW_NK(2, false); else VPS_PW_NK(1, false); }
 #undef VPS_PW_NK
 #undef VPS_PW_LAUNCH
-    return 1;
 }

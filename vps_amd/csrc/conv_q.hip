@@ -1,5 +1,5 @@
 // Uniform-lead MFMA convolution kernels (round 4): see the block comment below. Own translation unit (conv_mfma.hip takes ~5 minutes
-// to compile); entered through vpsi_launch_conv_q from launch_conv in conv_mfma.hip.
+// to compile); entered through vpsi_launch_conv_q from vps_conv2d in conv_mfma.hip.
 #include "conv_common.h"
 #include <cstdio>
 
@@ -298,41 +298,22 @@ void conv_mfma_bf16q_kernel(const vps_conv_desc d, const int M, const int tiles_
 
 }  // namespace
 
-int vpsi_launch_conv_pw(const vps_conv_desc& d, int M, int tiles_m, int tiles_n, hipStream_t s);
-
-// -> 1 if a uniform-lead instance exists for this launch and was enqueued, 0 if the caller has to use another kernel
+// VPS_DEBUG_OCC=1: resident blocks per CU of the two f16x3 instances on stderr (80 KB of LDS per block: two blocks need all 160 KB)
 __attribute__((visibility("hidden")))
-int vpsi_launch_conv_q(const vps_conv_desc& d_in, int M, int tiles_m, int tiles_n, int per_split, long nblk, bool tapmajor, hipStream_t s) {
-    const vps_conv_desc& d = d_in;
-    // 1x1 layers with at least two rounds of resident blocks: the persistent pointwise kernel (conv_pw.hip)
-    if (!tapmajor && vpsi_launch_conv_pw(d, M, tiles_m, tiles_n, s)) return 1;
-    // VPS_UNIFORM_LEAD in the environment (A/B runs): bit 0 = chunk-major layers (default on), bit 1 = tap-major layers (default off:
-    // the thin first layers measured 12 .. 23 % slower here than on the pipelined kernel - 3 .. 7 k-steps per tile, the longer prologue
-    // is not paid back)
-    static const int q_mode = getenv("VPS_UNIFORM_LEAD") ? atoi(getenv("VPS_UNIFORM_LEAD")) : 1;
-    if (!(q_mode & (tapmajor ? 2 : 1))) return 0;
-    if (d.offset || !(d.prec == VPS_PREC_F16X3 || d.prec == VPS_PREC_BF16X3 || d.prec == VPS_PREC_BF16)) return 0;
-    if (d.tile_n != 128 && d.tile_n != 64) return 0;
-    // VPS_DEBUG_OCC=1: resident blocks per CU of the two f16x3 instances, once, on stderr (80 KB of LDS per block: two blocks need all 160 KB)
-    static bool occ_done = false;
-    if (!occ_done && getenv("VPS_DEBUG_OCC")) {
-        occ_done = true;
-        int n128 = -1, n64 = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n128, conv_mfma_bf16q_kernel<2, 2, 2, 2, VPS_PREC_F16X3, false>, 256, 0);
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n64, conv_mfma_bf16q_kernel<2, 1, 2, 2, VPS_PREC_F16X3, false>, 256, 0);
-        fprintf(stderr, "[vps] uniform-lead kernel occupancy: %d blocks/CU (128-column tiles), %d (64-column tiles)\n", n128, n64);
-    }
-#define VPS_Q_LAUNCH(TN, MODE, TAP)                                                                                          \
-    hipLaunchKernelGGL((conv_mfma_bf16q_kernel<2, TN, 2, 2, MODE, TAP>), dim3((unsigned)nblk), dim3(256), 0, s, d, M, tiles_m, tiles_n, per_split)
-#define VPS_Q_MODE(MODE)                                                                                                     \
-    do {                                                                                                                     \
-        if (d.tile_n == 128) { if (tapmajor) VPS_Q_LAUNCH(2, MODE, true); else VPS_Q_LAUNCH(2, MODE, false); }               \
-        else { if (tapmajor) VPS_Q_LAUNCH(1, MODE, true); else VPS_Q_LAUNCH(1, MODE, false); }                               \
-    } while (0)
-    if (d.prec == VPS_PREC_BF16) VPS_Q_MODE(VPS_PREC_BF16);
-    else if (d.prec == VPS_PREC_BF16X3) VPS_Q_MODE(VPS_PREC_BF16X3);
-    else VPS_Q_MODE(VPS_PREC_F16X3);
-#undef VPS_Q_MODE
-#undef VPS_Q_LAUNCH
-    return 1;
+void vpsi_conv_q_debug_occ() {
+    int n128 = -1, n64 = -1;
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n128, conv_mfma_bf16q_kernel<2, 2, 2, 2, VPS_PREC_F16X3, false>, 256, 0);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n64, conv_mfma_bf16q_kernel<2, 1, 2, 2, VPS_PREC_F16X3, false>, 256, 0);
+    fprintf(stderr, "[vps] uniform-lead kernel occupancy: %d blocks/CU (128-column tiles), %d (64-column tiles)\n", n128, n64);
+}
+
+// chunk-major, non-deformable layers of the modes with two activation planes on 64- / 128-column tiles (TAPMAJOR = true, the tap-major
+// k order, has no instance any more: those layers measured slower here than on the pipelined kernel - conv_plan.cpp)
+__attribute__((visibility("hidden")))
+void vpsi_launch_conv_q(const vps_conv_desc& d, const conv_plan& p, hipStream_t s) {
+    with_prec<false>(d.prec, [&](auto mode) {
+        constexpr int MODE = decltype(mode)::value;
+        if (d.tile_n == 128) hipLaunchKernelGGL((conv_mfma_bf16q_kernel<2, 2, 2, 2, MODE, false>), dim3(p.grid), dim3(p.block), 0, s, d, p.M, p.tiles_m, p.tiles_n, p.per_split);
+        else hipLaunchKernelGGL((conv_mfma_bf16q_kernel<2, 1, 2, 2, MODE, false>), dim3(p.grid), dim3(p.block), 0, s, d, p.M, p.tiles_m, p.tiles_n, p.per_split);
+    });
 }

@@ -1,6 +1,6 @@
 // The narrow-output kernels of vps_conv2d (cout <= 4 in exact fp32 on the vector ALU: the FlowNet predict_flow / upsampled_flow layers, the RPN
-// objectness layer). Own translation unit since round 6; entered through vpsi_launch_conv_small from launch_conv (conv_mfma.hip), which
-// decides WHEN a layer comes here (cout <= 4, exact-fp32 descriptor, no offsets, no split-K, 32-column packing).
+// objectness layer). Own translation unit since round 6; entered through vpsi_launch_conv_small from vps_conv2d (conv_mfma.hip); conv_plan.cpp
+// decides WHEN a layer comes here (cout <= 4, exact-fp32 descriptor, no offsets, no split-K, 32-column packing) and which of the three kernels it gets.
 #include "conv_common.h"
 #include <cstdlib>
 
@@ -332,20 +332,10 @@ void conv_small3x3v_kernel(const vps_conv_desc d, const int runs_per_row, const 
 }  // namespace
 
 __attribute__((visibility("hidden")))
-void vpsi_launch_conv_small(const vps_conv_desc& d, const int M, hipStream_t s) {
-    int G = 1, logG = 0;
-    while (G < 64 && G < (d.cin_pad >> 2)) { G <<= 1; ++logG; }
-    const size_t wbytes = (size_t)(d.cout <= 2 ? 2 : 4) * d.kpad * sizeof(float);
-    if (d.KH == 3 && d.KW == 3 && d.stride == 1 && d.nclass == 1 && d.pad_y[0] == 1 && d.pad_x[0] == 1 && d.Ho == d.H && d.Wo == d.W &&
-        wbytes <= 150 * 1024 && (d.cout <= 2 || d.cout_pad >= 4) && (size_t)d.N * d.H * d.W * d.in_ld * sizeof(float) < 0xFFFFFFF0ull &&
-        (long)d.N * d.H * d.W < 0x7fffffffL) {               // 32-bit run index
+void vpsi_launch_conv_small(const vps_conv_desc& d, const conv_plan& p, hipStream_t s) {
+    const dim3 grid(p.grid), block(p.block);
+    if (p.kernel == CONV_K_SMALL3X3V) {
         constexpr int RUN = 4;
-        const int run = d.cout <= 2 ? RUN : RUN / 2;
-        const int runs_per_row = (d.W + run - 1) / run;
-        const long total_runs = (long)d.N * d.H * runs_per_row;
-        const int ppw = 64 >> logG;
-        long blocks = (total_runs + 4 * ppw - 1) / (4 * ppw);
-        if (blocks > 768) blocks = 768;               // 3 blocks of 4 waves per CU (152 VGPRs: all 18 loads of a run in flight): one resident round, the weights are staged once per block
 #define VPS_S3V(LG)                                                                                                                            \
         do {                                                                                                                               \
             static bool attr_v = false;                                                                                                    \
@@ -354,37 +344,19 @@ void vpsi_launch_conv_small(const vps_conv_desc& d, const int M, hipStream_t s) 
                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_small3x3v_kernel<4, RUN / 2, LG>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); \
                 attr_v = true;                                                                                                             \
             }                                                                                                                              \
-            if (d.cout <= 2) hipLaunchKernelGGL((conv_small3x3v_kernel<2, RUN, LG>), dim3((unsigned)blocks), dim3(256), wbytes, s, d, runs_per_row, (int)total_runs);      \
-            else hipLaunchKernelGGL((conv_small3x3v_kernel<4, RUN / 2, LG>), dim3((unsigned)blocks), dim3(256), wbytes, s, d, runs_per_row, (int)total_runs);           \
+            if (d.cout <= 2) hipLaunchKernelGGL((conv_small3x3v_kernel<2, RUN, LG>), grid, block, p.smem, s, d, p.runs_per_row, p.total_runs);      \
+            else hipLaunchKernelGGL((conv_small3x3v_kernel<4, RUN / 2, LG>), grid, block, p.smem, s, d, p.runs_per_row, p.total_runs);           \
         } while (0)
-        switch (logG) {
+        switch (p.logG) {
             case 0: VPS_S3V(0); break; case 1: VPS_S3V(1); break; case 2: VPS_S3V(2); break; case 3: VPS_S3V(3); break;
             case 4: VPS_S3V(4); break; case 5: VPS_S3V(5); break; default: VPS_S3V(6); break;
         }
 #undef VPS_S3V
-        return;
+    } else if (p.kernel == CONV_K_SMALL_BATCHED) {
+        if (d.cout <= 2) hipLaunchKernelGGL((conv_small_batched_kernel<2>), grid, block, p.smem, s, d, p.M, p.G, p.logG, p.nslot);
+        else hipLaunchKernelGGL((conv_small_batched_kernel<4>), grid, block, p.smem, s, d, p.M, p.G, p.logG, p.nslot);
+    } else {
+        if (d.cout <= 2) hipLaunchKernelGGL((conv_small_kernel<2>), grid, block, 0, s, d, p.M, p.G, p.logG);
+        else hipLaunchKernelGGL((conv_small_kernel<4>), grid, block, 0, s, d, p.M, p.G, p.logG);
     }
-    const long total = (long)d.nclass * M;
-    {   // eight loads per lane in flight, weights in LDS: conv_small_batched_kernel (VPS_SMALL_BATCHED=0: the one-load-per-step kernel, which also keeps
-        // the layers with fewer than eight loads per pixel - the 2 -> 2 up-flow layers measured 31 us there against 36 us here)
-        const char* e = getenv("VPS_SMALL_BATCHED");
-        const size_t wb = (size_t)d.nclass * (d.cout <= 2 ? 2 : 4) * d.kpad * sizeof(float);
-        if (!(e && e[0] == '0') && (d.cin_pad >> 2) * d.KH * d.KW >= 8 && wb <= 48 * 1024 && (d.cout <= 2 || d.cout_pad >= 4) && (size_t)d.N * d.H * d.W * d.in_ld * sizeof(float) < 0xFFFFFFF0ull) {
-            const int c4n = d.cin_pad >> 2, ntap = d.KH * d.KW;
-            int Gb = 1, logGb = 0;
-            while (Gb < 64 && Gb * 8 < c4n * ntap && Gb < c4n) { Gb <<= 1; ++logGb; }
-            const int nslot = (c4n + Gb - 1) >> logGb;
-            const int ppw = 64 >> logGb;
-            const long waves = (total + ppw - 1) / ppw;
-            long blocks = (waves + 3) / 4; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;   // 8 blocks per CU: one resident round
-            if (d.cout <= 2) hipLaunchKernelGGL((conv_small_batched_kernel<2>), dim3((unsigned)blocks), dim3(256), wb, s, d, M, Gb, logGb, nslot);
-            else hipLaunchKernelGGL((conv_small_batched_kernel<4>), dim3((unsigned)blocks), dim3(256), wb, s, d, M, Gb, logGb, nslot);
-            return;
-        }
-    }
-    long waves = (total + (64 >> logG) - 1) / (64 >> logG);
-    long blocks = (waves + 3) / 4; if (blocks > 8192) blocks = 8192; if (blocks < 1) blocks = 1;
-    if (d.cout <= 2) hipLaunchKernelGGL((conv_small_kernel<2>), dim3((unsigned)blocks), dim3(256), 0, s, d, M, G, logG);
-    else hipLaunchKernelGGL((conv_small_kernel<4>), dim3((unsigned)blocks), dim3(256), 0, s, d, M, G, logG);
-    return;
 }

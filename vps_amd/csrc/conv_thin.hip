@@ -239,47 +239,40 @@ void conv_thin_kernel(const vps_conv_desc d, const int tiles_x, const int tiles_
 }
 
 template <int C4, int KS, int S, int PH, int OCC, bool WRES>
-int launch_thin(const vps_conv_desc& d, hipStream_t s) {
-    const int tiles_x = (d.Qw + 31) / 32, tiles_y = (d.Qh + PH - 1) / PH;
-    const long ntiles = (long)d.N * tiles_x * tiles_y;
-    if (ntiles < 512 || ntiles > 0x7fffffffL) return 0;          // small maps: the pipelined kernels (split-K, fewer idle lanes)
-    constexpr int PR = (PH - 1) * S + KS, PC = 31 * S + KS, NK16 = (KS * C4 + 15) / 16;
-    constexpr size_t smem = (size_t)(2 * (PR * PC * C4 + 16) + (WRES ? KS : 1) * 2 * NK16 * 2 * 512) * 2 + 128 * sizeof(float);
-    static int resident = 0;                                      // blocks the chip holds at once
-    if (!resident) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_thin_kernel<C4, KS, S, PH, OCC, WRES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        int per_cu = 0, dev = 0, cus = 256;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv_thin_kernel<C4, KS, S, PH, OCC, WRES>, 256, smem);
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        resident = (per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 256);
-        if (getenv("VPS_DEBUG_OCC")) fprintf(stderr, "[vps] thin-input kernel <%d,%d,%d,%d>: %d blocks/CU, %zu B LDS\n", C4, KS, S, PH, per_cu, smem);
+struct Thin {
+    static constexpr int PR = (PH - 1) * S + KS, PC = 31 * S + KS, NK16 = (KS * C4 + 15) / 16;
+    static constexpr size_t smem = (size_t)(2 * (PR * PC * C4 + 16) + (WRES ? KS : 1) * 2 * NK16 * 2 * 512) * 2 + 128 * sizeof(float);
+    static void launch(const vps_conv_desc& d, const conv_plan& p, hipStream_t s) {
+        hipLaunchKernelGGL((conv_thin_kernel<C4, KS, S, PH, OCC, WRES>), dim3(p.grid), dim3(p.block), smem, s, d, p.tiles_n, p.tiles_m, p.ntiles);
     }
-    // whole rounds: every block walks the same number of tiles (+-1)
-    const long rounds = (ntiles + resident - 1) / resident;
-    const long grid = (ntiles + rounds - 1) / rounds;
-    hipLaunchKernelGGL((conv_thin_kernel<C4, KS, S, PH, OCC, WRES>), dim3((unsigned)grid), dim3(256), smem, s, d, tiles_x, tiles_y, (int)ntiles);
-    return 1;
-}
+    static int per_cu(bool debug) {      // also raises the kernel's dynamic-LDS limit: call before the first launch
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_thin_kernel<C4, KS, S, PH, OCC, WRES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        int n = 0;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_thin_kernel<C4, KS, S, PH, OCC, WRES>, 256, smem);
+        if (debug) fprintf(stderr, "[vps] thin-input kernel <%d,%d,%d,%d>: %d blocks/CU, %zu B LDS\n", C4, KS, S, PH, n, smem);
+        return n;
+    }
+};
+// the instances, in the order of conv_thin_shapes (conv_plan.cpp)
+typedef Thin<8, 3, 1, 8, 2, true> Thin0;
+typedef Thin<12, 3, 1, 8, 2, true> Thin1;
+typedef Thin<4, 7, 2, 8, 2, true> Thin2;
+typedef Thin<12, 7, 2, 4, 2, false> Thin3;
 
 }  // namespace
 
-// -> 1 if a thin-input instance exists for this launch and was enqueued, 0 if the caller has to use another kernel.
-// VPS_THIN=0 in the environment switches the family off (A/B runs).
 __attribute__((visibility("hidden")))
-int vpsi_launch_conv_thin(const vps_conv_desc& d, hipStream_t s) {
-    static const int on = getenv("VPS_THIN") ? atoi(getenv("VPS_THIN")) : 1;
-    if (!on || !d.w_thin || d.prec != VPS_PREC_F16X3 || d.offset || d.res || d.nclass != 1 || d.ksplit != 1 || d.korder != 0) return 0;
-    if (d.KH != d.KW || d.cout_pad != 64 || d.tile_n != 64 || (d.cout & 3) || ((uintptr_t)d.w_thin & 15)) return 0;
-    if (d.pad_y[0] != d.KH / 2 || d.pad_x[0] != d.KH / 2 || d.pad_y[1] != d.KH / 2 || d.pad_x[1] != d.KH / 2) return 0;
-    // the input is addressed through a 32-bit buffer resource: a narrow window inside a buffer of >= 4 GiB would wrap (loads beyond the
-    // truncated size return zeros, silently) -> the pipelined kernel takes such a launch
-    if ((size_t)d.N * d.H * d.W * d.in_ld * sizeof(float) >= 0xFFFFFFF0ull) return 0;
-    // float4 buffer stores: 16-byte aligned channel windows of an output below 4 GiB
-    if (((d.out_ld | d.out_coff) & 3) || ((uintptr_t)d.out & 15) || (size_t)d.N * d.Ho * d.Wo * d.out_ld * sizeof(float) >= 0xFFFFFFF0ull) return 0;
-    if (d.KH == 3 && d.stride == 1 && d.cin_pad == 8) return launch_thin<8, 3, 1, 8, 2, true>(d, s);
-    if (d.KH == 3 && d.stride == 1 && d.cin_pad == 12) return launch_thin<12, 3, 1, 8, 2, true>(d, s);
-    if (d.KH == 7 && d.stride == 2 && d.cin_pad == 4) return launch_thin<4, 7, 2, 8, 2, true>(d, s);
-    if (d.KH == 7 && d.stride == 2 && d.cin_pad == 12) return launch_thin<12, 7, 2, 4, 2, false>(d, s);
-    return 0;
+void vpsi_conv_thin_limits(conv_limits& lim, bool debug) {
+    lim.thin_per_cu[0] = Thin0::per_cu(debug); lim.thin_per_cu[1] = Thin1::per_cu(debug);
+    lim.thin_per_cu[2] = Thin2::per_cu(debug); lim.thin_per_cu[3] = Thin3::per_cu(debug);
+}
+
+__attribute__((visibility("hidden")))
+void vpsi_launch_conv_thin(const vps_conv_desc& d, const conv_plan& p, hipStream_t s) {
+    switch (p.thin) {
+        case 0: Thin0::launch(d, p, s); break;
+        case 1: Thin1::launch(d, p, s); break;
+        case 2: Thin2::launch(d, p, s); break;
+        default: Thin3::launch(d, p, s); break;
+    }
 }
