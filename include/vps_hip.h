@@ -479,6 +479,22 @@ int vps_segment_paint(const uint8_t* pan_2ch, int64_t npix, const uint8_t* lut, 
 int vps_pair_count(const uint8_t* gt_rgb, const uint8_t* pred_rgb, int64_t npix, const uint32_t* gt_ids, int ngt,
                    const uint32_t* pred_ids, int npred, int32_t* counts, void* stream);
 
+/* PNG output without a match search (csrc/png_ops.hip): a uint8 [H][W][C] DEVICE image, C = 1 or 3 in stored
+ * order, row stride in bytes -> one zlib stream for the IDAT chunk of an 8-bit grey / RGB PNG. The format is fixed:
+ *   filter   per row None (0), Sub (1) or Up (2) by the smallest sum of |int8(residual)|, a tie to the lower number; S = the rows in
+ *            order, each its filter byte + W*C residuals; N = H * (1 + W*C)
+ *   segments S in pieces of 8192 bytes, each coded alone: maximal runs of equal bytes; the first byte of a run is a literal, the other
+ *            R-1 are distance-1 matches of 258 while >= 258 remain, then one match of the rest if it is >= 3, else literals
+ *   bits     per segment a fixed-Huffman block (BFINAL 0) with those tokens and end-of-block, then an empty stored block
+ *            (pads to the byte, 00 00 FF FF): at most ceil(9*8192/8) + 7 bytes
+ *   stream   78 01, the segments, 03 00 (empty final fixed block), Adler-32 of S big-endian
+ * vps_png_encode_bound (HOST arithmetic only): worst-case stream bytes and the workspace bytes of vps_png_deflate.
+ * vps_png_deflate: every pointer is a DEVICE pointer (ws 16-byte, out_nbytes 8-byte aligned); launches on `stream`, no sync, no
+ * hidden allocation. out_nbytes[0] = bytes written, or -1 when out_capacity is too small (then nothing is stored to out). */
+int vps_png_encode_bound(int H, int W, int channels, int64_t* out_capacity, int64_t* ws_bytes);
+int vps_png_deflate(const uint8_t* img, int H, int W, int channels, int64_t row_stride, uint8_t* out, int64_t out_capacity,
+                    int64_t* out_nbytes, void* ws, int64_t ws_bytes, void* stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Input preparation: Normalize -> Pad(size_divisor) -> ImageToTensor of the test pipeline in one pass.
  * Replaces mmdet/datasets/pipelines/transforms.py:258-269, :310-318 and formating.py:52-67 (mmcv 0.2.14 imnormalize,

@@ -50,6 +50,7 @@ def parse_args(argv=None):
     ap.add_argument('--prec', default='f16x3', choices=['f32', 'bf16x6', 'f16x3'])
     ap.add_argument('--strict', action='store_true', help='load_checkpoint(strict=True): missing / unexpected keys are fatal')
     ap.add_argument('--png-workers', type=int, default=6)
+    ap.add_argument('--device-png', action='store_true', help='encode the result PNGs on the device (postprocess.DevicePngWriter) instead of PIL threads')
     ap.add_argument('--dry-run', action='store_true')
     ap.add_argument('--dry-size', default='128x256'); ap.add_argument('--dry-videos', type=int, default=1); ap.add_argument('--dry-frames', type=int, default=16)
     ap.add_argument('--check-only', action='store_true')
@@ -186,7 +187,12 @@ def run(args, tmp):
     kw = {}
     if args.dry_run:
         kw = dict(labeled_fid=args.dry_label_first, lambda_=5, nframes_per_video=len(names) // max(args.n_video, 1))
+    if args.device_png:
+        from vps_amd.postprocess import DevicePngWriter
+        kw['writer'] = DevicePngWriter(dev)
     pans, pj = inference_panoptic_video(pred_pans_2ch, output_dir, categories, names, n_video=args.n_video, color_generator=gen, device=dev, **kw)
+    if args.device_png:
+        kw['writer'].close()
     report['run'] = dict(frames=len(info), seconds=round(dt, 3), frames_per_s=round(len(info) / dt, 2), decodes=feeder.decodes, output_dir=output_dir,
                          png_files=len(os.listdir(os.path.join(output_dir, 'pan_pred'))))
     truth_dir, gt_json = args.truth_dir, args.pan_gt_json

@@ -93,9 +93,10 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False):
     return res, time.perf_counter() - t0
 
 
-def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper):
-    """test_vpq.py:178-198 with the device-side unifier / converter / asynchronous writer"""
-    from vps_amd.postprocess import PanopticUnifier, inference_panoptic_video
+def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_png=False):
+    """test_vpq.py:178-198 with the device-side unifier / converter / asynchronous writer (`device_png`: the PNGs are filtered and
+    deflated on the device too, postprocess.DevicePngWriter)"""
+    from vps_amd.postprocess import DevicePngWriter, PanopticUnifier, inference_panoptic_video
     unifier = PanopticUnifier(dev, 19, 9)
     two = unifier.get_unified_pan_result(res['all_ssegs'], res['all_panos'], res['all_pano_cls_inds'], obj_ids=res['all_pano_obj_ids'],
                                          stuff_area_limit=2048, names=res['all_names'])
@@ -103,8 +104,11 @@ def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper):
     pred_pans_2ch = [two[k] for k in keys]
     names = keys[(labeled_fid // lambda_)::lambda_]                               # names of the labelled frames (im_jsons['images'])
     cats = {c['id']: c for c in CATEGORIES}
+    writer = DevicePngWriter(dev) if device_png else None
     pans, pj = inference_panoptic_video(pred_pans_2ch, out_dir, CATEGORIES, names, n_video=videos, color_generator=ColorGenerator(cats), device=dev,
-                                        labeled_fid=labeled_fid, lambda_=lambda_, nframes_per_video=nper)
+                                        labeled_fid=labeled_fid, lambda_=lambda_, nframes_per_video=nper, writer=writer)
+    if writer is not None:
+        writer.close()
     return names, pans, pj
 
 
@@ -136,19 +140,20 @@ def main():
     ap.add_argument('--gt-prec', default=None, help='take the "ground truth" from a second run in this arithmetic mode (default: the prediction itself)')
     ap.add_argument('--separated', action='store_true', help='box classification layer of tests/golden/separated_fc_cls.npz (few, well-separated detections)')
     ap.add_argument('--out', default=os.path.join(ROOT, 'gpurun_out', 'vps_synth'))
+    ap.add_argument('--device-png', action='store_true', help='encode the result PNGs on the device (postprocess.DevicePngWriter) instead of PIL threads')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     labeled_fid, lambda_ = 20, 5
     nper = len(range(labeled_fid // lambda_, args.frames, lambda_))
     res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated)
     t0 = time.perf_counter()
-    names, pans, pj = postprocess(res, os.path.join(args.out, 'pred'), args.videos, dev, labeled_fid, lambda_, nper)
+    names, pans, pj = postprocess(res, os.path.join(args.out, 'pred'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png)
     dpost = time.perf_counter() - t0
     pred = (pans, pj)
     gt = pred
     if args.gt_prec:
         res2, _ = run_model(args.gt_prec, args.videos, args.frames, args.height, args.width, dev, args.separated)
-        _, pans2, pj2 = postprocess(res2, os.path.join(args.out, 'gt'), args.videos, dev, labeled_fid, lambda_, nper)
+        _, pans2, pj2 = postprocess(res2, os.path.join(args.out, 'gt'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png)
         gt = (pans2, pj2)
     t0 = time.perf_counter()
     score = vpq(gt, pred, args.videos, nper, dev)

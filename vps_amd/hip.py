@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VPS_HIP_LIB: developer override to load an experimental build of the same ABI (kernel A/B timing)
 LIB_PATH = os.environ.get('VPS_HIP_LIB') or os.path.join(_HERE, 'csrc', 'libvpship.so')
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 PREC_F32, PREC_BF16, PREC_BF16X3, PREC_BF16X6, PREC_F16X3 = 0, 1, 2, 3, 4
@@ -29,6 +29,7 @@ SYMBOLS = [
     'vps_panoptic_combine_dev', 'vps_rpn_select', 'vps_rpn_collect', 'vps_maskroi_select', 'vps_maskroi_finish', 'vps_track_assign', 'vps_pan_instances',
     'vps_unify_hist', 'vps_unify_tables', 'vps_unify_write', 'vps_image_prep', 'vps_resize_u8', 'vps_segment_stats', 'vps_segment_paint', 'vps_pair_count',
     'vps_png_info', 'vps_png_decode_bgr8', 'vps_jpeg_info', 'vps_jpeg_decode_coef', 'vps_jpeg_reconstruct',
+    'vps_png_encode_bound', 'vps_png_deflate',
 ]
 
 
@@ -190,6 +191,8 @@ def load():
         h.vps_jpeg_decode_coef.argtypes = [c_void_p, c_int64, c_void_p, c_int64]
     lib.vps_jpeg_reconstruct.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_int64, c_void_p,
                                          c_void_p]
+    lib.vps_png_encode_bound.argtypes = [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]
+    lib.vps_png_deflate.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]
     lib.vps_rpn_select.argtypes = [POINTER(c_void_p), POINTER(c_int32), POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
                                    POINTER(c_float), c_int, c_int, c_void_p, c_int, POINTER(c_float), c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vps_rpn_collect.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]

@@ -120,8 +120,13 @@ class TrackConverter:
         self.lut = torch.zeros(65536 * 3, dtype=torch.uint8, device=self.device)
 
     def convert(self, pan_2ch_set, color_generator):
+        annotations, pan_dev, _ = self.convert_device(pan_2ch_set, color_generator)
+        return annotations, [p.cpu().numpy() for p in pan_dev]
+
+    def convert_device(self, pan_2ch_set, color_generator):
+        """as `convert`, but the painted maps stay on the device: (annotations, pan_pred device tensors, pan_2ch device tensors)"""
         lib = hip.load()
-        annotations, pan_all = [], []
+        annotations, pan_all, two_all = [], [], []
         inst2color = {}
         for pan_2ch in pan_2ch_set:
             t = torch.from_numpy(np.ascontiguousarray(pan_2ch)) if isinstance(pan_2ch, np.ndarray) else pan_2ch
@@ -161,9 +166,10 @@ class TrackConverter:
             self.lut.copy_(torch.from_numpy(lut.reshape(-1)), non_blocking=False)
             out = torch.empty(H, W, 3, dtype=torch.uint8, device=self.device)
             hip.check(lib.vps_segment_paint(hip.ptr(t), H * W, hip.ptr(self.lut), hip.ptr(out), hip.stream_ptr()), 'vps_segment_paint')
-            pan_all.append(out.cpu().numpy())
+            pan_all.append(out)
+            two_all.append(t)
             annotations.append({"segments_info": [v for k, v in segm_info.items()]})
-        return annotations, pan_all
+        return annotations, pan_all, two_all
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -197,6 +203,164 @@ class AsyncPngWriter:
         return names
 
 
+def _png_view(t):
+    """device uint8 [H,W] / [H,W,3] with unit-stride pixels (rows may be strided) -> (tensor, H, W, C, row stride in bytes)"""
+    assert torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8, 'png_deflate takes a device uint8 tensor'
+    assert t.dim() == 2 or (t.dim() == 3 and t.shape[2] in (1, 3)), 'shape [H,W] or [H,W,3], got %s' % (tuple(t.shape),)
+    C = 1 if t.dim() == 2 else int(t.shape[2])
+    H, W = int(t.shape[0]), int(t.shape[1])
+    dense = (t.stride(1) == 1) if t.dim() == 2 else (t.stride(2) == 1 and t.stride(1) == C)
+    if not (dense and t.stride(0) >= W * C):
+        t = t.contiguous()
+    return t, H, W, C, int(t.stride(0)) if H > 1 else W * C
+
+
+def png_encode_bound(H, W, channels):
+    """(worst-case stream bytes, workspace bytes) of `vps_png_deflate` for one image size"""
+    import ctypes
+    cap, wsb = ctypes.c_int64(0), ctypes.c_int64(0)
+    hip.check(hip.load().vps_png_encode_bound(H, W, channels, ctypes.byref(cap), ctypes.byref(wsb)), 'vps_png_encode_bound')
+    return cap.value, wsb.value
+
+
+def png_deflate(t, out=None, ws=None, size=None):
+    """Filter + deflate a device uint8 [H,W,3] / [H,W] map on the device (`vps_png_deflate`: literals and distance-1 runs in the fixed
+    Huffman code) on the current stream, no sync. Returns (device uint8 buffer, device int64 [1] size): the zlib
+    stream is buffer[:size]; size -1 = `out` was too small. `out` / `ws` / `size`: caller-owned buffers (default: fresh worst-case ones)."""
+    t, H, W, C, stride = _png_view(t)
+    if out is None or ws is None:
+        cap, wsb = png_encode_bound(H, W, C)
+        out = torch.empty(cap, dtype=torch.uint8, device=t.device) if out is None else out
+        ws = torch.empty(wsb, dtype=torch.uint8, device=t.device) if ws is None else ws
+    if size is None:
+        size = torch.empty(1, dtype=torch.int64, device=t.device)
+    hip.check(hip.load().vps_png_deflate(hip.ptr(t), H, W, C, stride, hip.ptr(out), out.numel(), hip.ptr(size), hip.ptr(ws), ws.numel(),
+                                         hip.stream_ptr()), 'vps_png_deflate')
+    return out, size
+
+
+def png_container(stream_bytes, H, W, channels):
+    """the PNG file around one zlib stream: signature, IHDR (8 bit, grey or RGB, no interlace), one IDAT, IEND. The CRCs are zlib.crc32
+    on the host: the compressed data is ~100 KB."""
+    import struct
+    import zlib
+
+    def chunk(tag, data):
+        return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xFFFFFFFF)
+    ihdr = struct.pack('>IIBBBBB', W, H, 8, {1: 0, 3: 2}[channels], 0, 0, 0)
+    return b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', ihdr) + chunk(b'IDAT', bytes(stream_bytes)) + chunk(b'IEND', b'')
+
+
+class _PngSlot:
+    def __init__(self, device):
+        self.device = device
+        self.cap = self.wsb = 0
+        self.out = self.ws = self.host = self.image = None
+        self.size = torch.empty(1, dtype=torch.int64, device=device)
+        self.size_host = torch.empty(1, dtype=torch.int64).pin_memory()
+        self.event = torch.cuda.Event()
+
+    def fit(self, cap, wsb):
+        if cap > self.cap:
+            self.out, self.cap = torch.empty(cap, dtype=torch.uint8, device=self.device), cap
+        if wsb > self.wsb:
+            self.ws, self.wsb = torch.empty(wsb, dtype=torch.uint8, device=self.device), wsb
+
+    def staging(self, n):
+        if self.host is None or self.host.numel() < n:
+            self.host = torch.empty(max(1 << 16, 1 << (n - 1).bit_length()), dtype=torch.uint8).pin_memory()
+        return self.host[:n]
+
+
+class DevicePngWriter:
+    """`AsyncPngWriter`'s surface with the encoding on the device: `submit(device tensor, name)` enqueues `png_deflate` on the CURRENT
+    stream into one of `slots` ring slots (output + workspace, sized by `vps_png_encode_bound` from the first image and grown if a
+    larger one comes), copies the size to pinned memory, records an event and returns - it never synchronises the caller's stream and
+    blocks only while every slot is busy. A worker thread waits for the event, copies exactly `size` bytes on its own copy stream,
+    wraps them (`png_container`) and writes the file. Host arrays - and an image whose stream did not fit (size -1) - go through PIL
+    like `AsyncPngWriter`. Counters: `device_encoded`, `fallback_encoded`. `close()` joins and re-raises a worker's exception."""
+    accepts_device = True
+
+    def __init__(self, device='cuda', workers=2, slots=8):
+        import queue
+        import threading
+        from concurrent.futures import ThreadPoolExecutor
+        self.device = torch.device(device)
+        self.pool = ThreadPoolExecutor(max_workers=workers)
+        self.futures = []
+        self.free = queue.Queue()
+        for _ in range(slots):
+            self.free.put(_PngSlot(self.device))
+        self.local = threading.local()
+        self.lock = threading.Lock()
+        self.device_encoded = 0      # files whose stream came from vps_png_deflate
+        self.fallback_encoded = 0    # files PIL encoded (host input, or a stream that did not fit)
+
+    def _count(self, device):
+        with self.lock:
+            if device:
+                self.device_encoded += 1
+            else:
+                self.fallback_encoded += 1
+
+    def _save_host(self, image, name):
+        AsyncPngWriter._save(image, name)
+        self._count(False)
+        return name
+
+    def _finish(self, slot, name, H, W, C):
+        try:
+            slot.event.synchronize()                     # the worker waits, not the caller
+            n = int(slot.size_host[0])
+            if not hasattr(self.local, 'stream'):
+                self.local.stream = torch.cuda.Stream(self.device)
+            with torch.cuda.stream(self.local.stream):
+                if n < 0:
+                    host = slot.image.cpu().numpy()
+                else:
+                    host = slot.staging(n)
+                    host.copy_(slot.out[:n], non_blocking=True)
+                    self.local.stream.synchronize()
+                    data = png_container(host.numpy().tobytes(), H, W, C)
+        finally:
+            slot.image = None
+            self.free.put(slot)
+        if n < 0:
+            return self._save_host(host, name)
+        os.makedirs(os.path.dirname(name) or '.', exist_ok=True)
+        with open(name, 'wb') as f:
+            f.write(data)
+        self._count(True)
+        return name
+
+    def submit(self, image, name):
+        if not (torch.is_tensor(image) and image.is_cuda):
+            image = image.numpy() if torch.is_tensor(image) else image
+            self.futures.append(self.pool.submit(self._save_host, np.ascontiguousarray(image), name))
+            return
+        t, H, W, C, _ = _png_view(image)
+        slot = self.free.get()                           # blocks only when every slot is in flight
+        try:
+            slot.fit(*png_encode_bound(H, W, C))
+            slot.image = t                               # alive until the worker is done with it
+            png_deflate(t, slot.out, slot.ws, slot.size)
+            slot.size_host.copy_(slot.size, non_blocking=True)
+            slot.event.record()
+        except BaseException:
+            slot.image = None
+            self.free.put(slot)
+            raise
+        self.futures.append(self.pool.submit(self._finish, slot, name, H, W, C))
+
+    def close(self):
+        futures, self.futures = self.futures, []
+        try:
+            names = [f.result() for f in futures]        # re-raises a worker's exception
+        finally:
+            self.pool.shutdown()
+        return names
+
+
 def png_name(save_folder, name):
     """cityscapes_vps.py:73 (save_image): output file name of an input image name"""
     return os.path.join(save_folder, name.replace('_leftImg8bit', '').replace('_newImg8bit', '').replace('jpg', 'png').replace('jpeg', 'png'))
@@ -218,15 +382,20 @@ def inference_panoptic_video(pred_pans_2ch, output_dir, categories, names, n_vid
     own = writer is None
     writer = AsyncPngWriter() if own else writer
     conv = TrackConverter(device)
+    on_device = bool(getattr(writer, 'accepts_device', False))     # DevicePngWriter: hand over the device maps, not host copies
     annotations, pan_all = [], []
     for v0 in range(0, len(pred_pans_2ch), nframes_per_video):
         chunk = pred_pans_2ch[v0:v0 + nframes_per_video]
-        ann, pans = conv.convert(chunk, color_generator)
-        for j, (a, pan) in enumerate(zip(ann, pans)):
+        ann, pans_dev, twos_dev = conv.convert_device(chunk, color_generator)
+        for j, (a, pan_dev) in enumerate(zip(ann, pans_dev)):
             i = v0 + j
             annotations.append(a)
+            if names is not None and on_device:
+                writer.submit(twos_dev[j], png_name(os.path.join(output_dir, 'pan_2ch'), names[i]))
+                writer.submit(pan_dev, png_name(os.path.join(output_dir, 'pan_pred'), names[i]))
+            pan = pan_dev.cpu().numpy()                            # part of the return value: downloaded once either way
             pan_all.append(pan)
-            if names is not None:
+            if names is not None and not on_device:
                 two = chunk[j]
                 two = two.cpu().numpy() if torch.is_tensor(two) else np.asarray(two)
                 writer.submit(two, png_name(os.path.join(output_dir, 'pan_2ch'), names[i]))
