@@ -479,6 +479,32 @@ int vps_segment_paint(const uint8_t* pan_2ch, int64_t npix, const uint8_t* lut, 
 int vps_pair_count(const uint8_t* gt_rgb, const uint8_t* pred_rgb, int64_t npix, const uint32_t* gt_ids, int ngt,
                    const uint32_t* pred_ids, int npred, int32_t* counts, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Image-level evaluation (csrc/ipq_ops.hip): the device passes behind tools/test_eval_ipq.py.
+ *
+ * vps_unify_tables_image: vps_unify_tables for tools/dataset/base_dataset.py:239-267 (BaseDataset.get_unified_pan_result): the same
+ * decisions, no object ids, channel 2 of the table is 0. Between vps_unify_hist and vps_unify_write, which are shared.
+ *
+ * vps_segment_stats_ch / vps_segment_paint_ch: vps_segment_stats / vps_segment_paint with the segment id read from channel
+ * id_channel (1 or 2): key = pan_2ch[.., 0] * 256 + pan_2ch[.., id_channel]. Channel 1 is the key of _converter_2ch_single_core
+ * (base_dataset.py:296, 1000 * pan_seg + pan_ins). Same `stats` and `lut` layouts.
+ *
+ * vps_sseg_confusion: one image of Cityscapes.evaluate_ssegs (tools/dataset/cityscapes.py:120-135) with get_confusion_matrix
+ * (base_dataset.py:449-467).
+ *   gt      uint8 [Hg][Wg] label map (255 = ignored), pred uint8 [Hp][Wp] prediction
+ *   ytab    int32 [Hg], xtab int32 [Wg]: source row / column of every label row / column (Pillow's NEAREST resize of pred to the
+ *           label's size; values are clamped to the prediction). Both NULL = identity, sizes must then be equal.
+ *   counts  int64 [class_num][class_num], DEVICE, caller-owned: the call ADDS to it and never zeroes it, so a whole validation set
+ *           accumulates without a synchronisation. For gt != 255: idx = gt * class_num + pred, counted when idx < class_num^2
+ *           (a prediction >= class_num lands in a later cell, as the reference's bincount puts it).
+ *   class_num 1..32, otherwise -1001 and nothing is launched; Hg * Wg < 2^31. */
+int vps_unify_tables_image(const int32_t* hist, const int32_t* pan_count, const int32_t* cls_ind, int k, int id_last_stuff,
+                           int64_t stuff_area_limit, uint8_t* tables, int32_t* status, void* stream);
+int vps_segment_stats_ch(const uint8_t* pan_2ch, int H, int W, int id_channel, int32_t* stats, void* stream);
+int vps_segment_paint_ch(const uint8_t* pan_2ch, int64_t npix, int id_channel, const uint8_t* lut, uint8_t* out, void* stream);
+int vps_sseg_confusion(const uint8_t* gt, int Hg, int Wg, const uint8_t* pred, int Hp, int Wp, const int32_t* ytab,
+                       const int32_t* xtab, int class_num, int64_t* counts, void* stream);
+
 /* PNG output without a match search (csrc/png_ops.hip): a uint8 [H][W][C] DEVICE image, C = 1 or 3 in stored
  * order, row stride in bytes -> one zlib stream for the IDAT chunk of an 8-bit grey / RGB PNG. The format is fixed:
  *   filter   per row None (0), Sub (1) or Up (2) by the smallest sum of |int8(residual)|, a tie to the lower number; S = the rows in

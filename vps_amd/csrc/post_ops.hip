@@ -67,7 +67,7 @@ void unify_hist_kernel(const uint8_t* __restrict__ pan, const uint8_t* __restric
 __global__ __launch_bounds__(1024)
 void unify_tables_kernel(const int32_t* __restrict__ hist, const int32_t* __restrict__ pan_count, const int32_t* __restrict__ cls_ind,
                          int k, const int32_t* __restrict__ obj_id, int nobj, int id_last_stuff, long stuff_area_limit,
-                         uint8_t* __restrict__ tables, int32_t* __restrict__ status) {
+                         uint8_t* __restrict__ tables, int32_t* __restrict__ status, int image_level) {
     __shared__ int seg_t[256], ins_t[256], obj_t[256], pcnt[256], top_c[256], top_n[256], cls_l[256], oid_l[256];
     __shared__ long tot[256], area[256];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -154,7 +154,8 @@ void unify_tables_kernel(const int32_t* __restrict__ hist, const int32_t* __rest
         if (c <= id_last_stuff && area[c] > 0 && area[c] < stuff_area_limit) sv = 255;
         tables[t] = (uint8_t)sv;
         tables[256 + t] = (uint8_t)ins_t[t];
-        tables[512 + t] = (uint8_t)obj_t[t];           // uint8 maps: values wrap modulo 256 like the reference's in-place stores
+        // uint8 maps: values wrap modulo 256 like the reference's in-place stores. image_level: base_dataset.py:269-271 leaves channel 2 zero
+        tables[512 + t] = image_level ? (uint8_t)0 : (uint8_t)obj_t[t];
     }
 }
 
@@ -206,7 +207,18 @@ extern "C" int vps_unify_tables(const int32_t* hist, const int32_t* pan_count, c
     if (!hist || !pan_count || !tables || !status || k < 0 || (k > 0 && !cls_ind) || nobj < 0 || id_last_stuff < 0 || id_last_stuff > 254)
         return VPS_EARG(1);
     hipLaunchKernelGGL(unify_tables_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, hist, pan_count, cls_ind, k, obj_id, nobj,
-                       id_last_stuff, (long)stuff_area_limit, tables, status);
+                       id_last_stuff, (long)stuff_area_limit, tables, status, 0);
+    return vps_launch_status();
+}
+
+// tools/dataset/base_dataset.py:239-267 (BaseDataset.get_unified_pan_result, the image-level driver's): the same decisions without
+// object ids, and a table whose channel 2 is 0
+extern "C" int vps_unify_tables_image(const int32_t* hist, const int32_t* pan_count, const int32_t* cls_ind, int k, int id_last_stuff,
+                                      int64_t stuff_area_limit, uint8_t* tables, int32_t* status, void* stream) {
+    if (!hist || !pan_count || !tables || !status || k < 0 || (k > 0 && !cls_ind) || id_last_stuff < 0 || id_last_stuff > 254)
+        return VPS_EARG(1);
+    hipLaunchKernelGGL(unify_tables_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, hist, pan_count, cls_ind, k,
+                       (const int32_t*)nullptr, 0, id_last_stuff, (long)stuff_area_limit, tables, status, 1);
     return vps_launch_status();
 }
 

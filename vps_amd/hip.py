@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VPS_HIP_LIB: developer override to load an experimental build of the same ABI (kernel A/B timing)
 LIB_PATH = os.environ.get('VPS_HIP_LIB') or os.path.join(_HERE, 'csrc', 'libvpship.so')
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 PREC_F32, PREC_BF16, PREC_BF16X3, PREC_BF16X6, PREC_F16X3 = 0, 1, 2, 3, 4
@@ -30,6 +30,7 @@ SYMBOLS = [
     'vps_unify_hist', 'vps_unify_tables', 'vps_unify_write', 'vps_image_prep', 'vps_resize_u8', 'vps_segment_stats', 'vps_segment_paint', 'vps_pair_count',
     'vps_png_info', 'vps_png_decode_bgr8', 'vps_jpeg_info', 'vps_jpeg_decode_coef', 'vps_jpeg_reconstruct',
     'vps_png_encode_bound', 'vps_png_deflate',
+    'vps_unify_tables_image', 'vps_segment_stats_ch', 'vps_segment_paint_ch', 'vps_sseg_confusion',
 ]
 
 
@@ -212,6 +213,10 @@ def load():
     lib.vps_segment_stats.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p]
     lib.vps_segment_paint.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
     lib.vps_pair_count.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]
+    lib.vps_unify_tables_image.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p]
+    lib.vps_segment_stats_ch.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+    lib.vps_segment_paint_ch.argtypes = [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]
+    lib.vps_sseg_confusion.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
     _lib = lib
     return lib
 

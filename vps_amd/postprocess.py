@@ -187,10 +187,13 @@ class AsyncPngWriter:
         self.futures = []
 
     @staticmethod
-    def _save(image, name):
+    def _save(image, name, palette=None):
         from PIL import Image
         os.makedirs(os.path.dirname(name) or '.', exist_ok=True)
-        Image.fromarray(image).save(name)
+        im = Image.fromarray(image)
+        if palette is not None:
+            im.putpalette(np.asarray(palette, dtype=np.uint8).reshape(-1))
+        im.save(name)
         return name
 
     def submit(self, image, name):
@@ -239,16 +242,23 @@ def png_deflate(t, out=None, ws=None, size=None):
     return out, size
 
 
-def png_container(stream_bytes, H, W, channels):
+def png_container(stream_bytes, H, W, channels, palette=None):
     """the PNG file around one zlib stream: signature, IHDR (8 bit, grey or RGB, no interlace), one IDAT, IEND. The CRCs are zlib.crc32
-    on the host: the compressed data is ~100 KB."""
+    on the host: the compressed data is ~100 KB. `palette` (uint8 [256][3], single-channel images only): colour type 3 with a PLTE
+    chunk in front of the same IDAT stream - the file `Image.putpalette(palette)` + `save` gives in content."""
     import struct
     import zlib
 
     def chunk(tag, data):
         return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xFFFFFFFF)
-    ihdr = struct.pack('>IIBBBBB', W, H, 8, {1: 0, 3: 2}[channels], 0, 0, 0)
-    return b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', ihdr) + chunk(b'IDAT', bytes(stream_bytes)) + chunk(b'IEND', b'')
+    plte = b''
+    ctype = {1: 0, 3: 2}[channels]
+    if palette is not None:
+        pal = np.ascontiguousarray(np.asarray(palette, dtype=np.uint8).reshape(-1))
+        assert channels == 1 and pal.size == 768, 'a palette is 256 x 3 uint8 and goes with a single-channel image'
+        ctype, plte = 3, chunk(b'PLTE', pal.tobytes())
+    ihdr = struct.pack('>IIBBBBB', W, H, 8, ctype, 0, 0, 0)
+    return b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', ihdr) + plte + chunk(b'IDAT', bytes(stream_bytes)) + chunk(b'IEND', b'')
 
 
 class _PngSlot:
@@ -303,12 +313,12 @@ class DevicePngWriter:
             else:
                 self.fallback_encoded += 1
 
-    def _save_host(self, image, name):
-        AsyncPngWriter._save(image, name)
+    def _save_host(self, image, name, palette=None):
+        AsyncPngWriter._save(image, name, palette)
         self._count(False)
         return name
 
-    def _finish(self, slot, name, H, W, C):
+    def _finish(self, slot, name, H, W, C, palette=None):
         try:
             slot.event.synchronize()                     # the worker waits, not the caller
             n = int(slot.size_host[0])
@@ -321,24 +331,26 @@ class DevicePngWriter:
                     host = slot.staging(n)
                     host.copy_(slot.out[:n], non_blocking=True)
                     self.local.stream.synchronize()
-                    data = png_container(host.numpy().tobytes(), H, W, C)
+                    data = png_container(host.numpy().tobytes(), H, W, C, palette)
         finally:
             slot.image = None
             self.free.put(slot)
         if n < 0:
-            return self._save_host(host, name)
+            return self._save_host(host, name, palette)
         os.makedirs(os.path.dirname(name) or '.', exist_ok=True)
         with open(name, 'wb') as f:
             f.write(data)
         self._count(True)
         return name
 
-    def submit(self, image, name):
+    def submit(self, image, name, palette=None):
+        """`palette` (uint8 [256][3], optional, [H,W] maps only): a palette PNG, as `putpalette` + `save`"""
         if not (torch.is_tensor(image) and image.is_cuda):
             image = image.numpy() if torch.is_tensor(image) else image
-            self.futures.append(self.pool.submit(self._save_host, np.ascontiguousarray(image), name))
+            self.futures.append(self.pool.submit(self._save_host, np.ascontiguousarray(image), name, palette))
             return
         t, H, W, C, _ = _png_view(image)
+        assert palette is None or C == 1, 'a palette goes with a single-channel map'
         slot = self.free.get()                           # blocks only when every slot is in flight
         try:
             slot.fit(*png_encode_bound(H, W, C))
@@ -350,7 +362,7 @@ class DevicePngWriter:
             slot.image = None
             self.free.put(slot)
             raise
-        self.futures.append(self.pool.submit(self._finish, slot, name, H, W, C))
+        self.futures.append(self.pool.submit(self._finish, slot, name, H, W, C, palette))
 
     def close(self):
         futures, self.futures = self.futures, []
