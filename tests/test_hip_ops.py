@@ -457,7 +457,7 @@ def test_persistent_pointwise_kernel_is_bitwise_the_uniform_lead_kernel(dev, cin
         r = nhwc.FMap(torch.randn(1, Ho >> rs, Wo >> rs, cout, generator=g).to(dev), cout, 0)
 
     def run():
-        pc.__dict__.pop('_dcache', None)
+        pc.forget_launches()
         out = nhwc.FMap(torch.full((1, Ho, Wo, cout), 7.0, device=dev), cout, 0)
         pc(x, out=out, ws=nhwc.Workspace(dev), res=r, res_shift=rs)
         torch.cuda.synchronize()
@@ -490,7 +490,7 @@ def test_pipelined_8_wave_halo_kernel_is_bitwise_conv_mfma_h8(dev, cin, cout, H,
     r = nhwc.FMap(torch.randn(1, H, W, cout, generator=g).to(dev), cout, 0) if res else None
 
     def run():
-        pc.__dict__.pop('_dcache', None)
+        pc.forget_launches()
         out = nhwc.FMap(torch.full((1, H, W, cout), 7.0, device=dev), cout, 0)
         pc(x, out=out, ws=nhwc.Workspace(dev), res=r)
         torch.cuda.synchronize()
@@ -521,7 +521,7 @@ def test_transposed_16_column_layer_with_the_four_classes_in_one_block_is_bitwis
     try:
         for mode in ('0', '1'):
             os.environ['VPS_N16T'] = mode
-            pc.__dict__.pop('_dcache', None)
+            pc.forget_launches()
             o = pc(xin, ws=nhwc.Workspace(dev), name='o')
             torch.cuda.synchronize()
             outs[mode] = o.t.clone()
@@ -553,7 +553,7 @@ def test_17_to_32_column_layers_on_the_two_column_block_kernel(dev, cin, cout, k
     try:
         for mode in ('0', '1'):
             os.environ['VPS_N32'] = mode
-            pc.__dict__.pop('_dcache', None)
+            pc.forget_launches()
             o = pc(xin, ws=nhwc.Workspace(dev), name='o')
             torch.cuda.synchronize()
             outs[mode] = o.to_nchw().cpu()

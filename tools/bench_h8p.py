@@ -46,7 +46,7 @@ def main():
         outs, us = {}, {}
         for mode in ('0', '1'):
             os.environ['VPS_H8P'] = mode
-            pc.__dict__.pop('_dcache', None)
+            pc.forget_launches()
             out = nhwc.FMap(torch.zeros(1, H, W, cout, device=dev), cout, 0)
             us[mode] = run(pc, x, out, ws, res, 10)
             outs[mode] = out.t.clone()

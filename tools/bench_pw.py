@@ -60,7 +60,7 @@ def main():
         outs, us = {}, {}
         for mode in ('0', '1'):
             os.environ['VPS_PW'] = mode
-            pc.__dict__.pop('_dcache', None)
+            pc.forget_launches()
             out = nhwc.FMap(torch.zeros(1, Ho, Wo, cout, device=dev), cout, 0)
             us[mode] = run(pc, x, out, ws, res, rs, 20)
             outs[mode] = out.t.clone()

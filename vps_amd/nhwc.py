@@ -5,8 +5,8 @@ Layout: every activation is a device tensor [N, H, W, ld] fp32; a feature map (`
 (FlowNet2 decoders, LiteFlowNet input, TCEA stack, UPSNet head) never materialise. Pad channels of a buffer are
 zero (buffers come from `Workspace.get(..., zero=True)` once and pads are never written).
 """
+import collections
 import ctypes
-import math
 import os
 import weakref
 from ctypes import c_float, c_int, c_void_p
@@ -305,6 +305,66 @@ def _tile_n(cout):
     return 32 if cout <= 32 else (64 if cout <= 64 else 128)
 
 
+def _pack_taps(wt, cin_pad, korder):
+    """wt [O, ntap, I] -> [O, K] in the kernel's k order (see vps_conv_desc.korder)"""
+    O, ntap, I = wt.shape
+    if korder == 0:                                        # tap-major: k = tap*cin_pad + ci
+        wp = torch.zeros(O, ntap, cin_pad)
+        wp[..., :I] = wt
+        return wp.reshape(O, ntap * cin_pad)
+    nch = (cin_pad + 31) // 32                             # chunk-major: k = (chunk*ntap + tap)*32 + c
+    wp = torch.zeros(O, ntap, nch * 32)
+    wp[..., :I] = wt
+    return wp.view(O, ntap, nch, 32).permute(0, 2, 1, 3).reshape(O, nch * ntap * 32)
+
+
+# what one launch of a layer on a map of a given size looks like: the column tile, the split-K count, the channels per GroupNorm
+# group if the epilogue takes the sums (0: it does not), and the sizes of the split-K partial-sum scratch and ticket buffers
+ConvGeometry = collections.namedtuple('ConvGeometry', 'tile_n ksplit gn_cpg scratch_floats tickets')
+_Launch = collections.namedtuple('_Launch', 'desc keep')     # a cached launch: the filled descriptor and the tensors it points into
+
+
+def _chunk_consistent_split(nch, target):
+    """the largest split count <= target that ceil-division of `nch` chunks reproduces: k ranges of ceil(nch / k) chunks leave
+    ceil(nch / ceil(nch / k)) of them non-empty, and `chunk_split` in csrc/conv_plan.cpp rejects any other count (VPS_EARG 20)"""
+    return max(k for k in range(1, target + 1) if -(-nch // -(-nch // k)) == k)
+
+
+def conv_geometry(layer, N, Qh, Qw, out_ld, out_coff, has_res, gn_groups):
+    """ConvGeometry of `layer` (a PackedConv) on N maps of Qh x Qw output pixels per parity class. out_ld / out_coff / has_res /
+    gn_groups (None: the caller wants no GroupNorm sums): what decides whether the epilogue can take the sums - the conditions
+    vps_conv2d checks again (VPS_EARG 15)."""
+    M = N * Qh * Qw
+    mtiles = (M + 127) // 128
+    # deformable layers with a multiple of 256 output channels on the large maps: one block computes all 256 columns of its
+    # 128 pixels, so the bilinear loader runs once per pixel tile instead of once per 128 columns (conv_mfma.hip, tile_n 256)
+    wide = (DCN256[0] and layer.deform and layer.prec == hip.PREC_F16X3 and layer.korder == 1 and layer.cout_pad % 256 == 0
+            and mtiles * (layer.cout_pad // 256) >= DCN256_MIN_TILES)
+    tile_n = 256 if wide else layer.tile_n
+    # split-K for launches that cannot fill 256 CUs
+    tiles = mtiles * (layer.cout_pad // tile_n) * layer.nclass
+    ksteps = layer.kpad // 32
+    ksplit = 1
+    if tiles < 256 and ksteps >= 8 and not layer.small:
+        ksplit = max(1, min((SPLITK_TARGET_BLOCKS + tiles - 1) // tiles, ksteps // 4, 32))
+        if layer.korder == 1:
+            # chunk-major layers split over whole 32-channel chunks; the ranges may be uneven (the last split is shorter)
+            ksplit = _chunk_consistent_split(ksteps // (layer.KH * layer.KW), ksplit)
+        else:
+            per = (ksteps + ksplit - 1) // ksplit
+            ksplit = (ksteps + per - 1) // per
+    gn_cpg = 0
+    if (gn_groups is not None and layer.deform and layer.prec != hip.PREC_F32 and ksplit == 1 and not has_res
+            and not ((layer.cout | out_ld | out_coff) & 3) and layer.cout % gn_groups == 0):
+        cpg = layer.cout // gn_groups
+        gn_cpg = cpg if cpg == 4 or cpg % 8 == 0 else 0
+    if ksplit == 1:
+        return ConvGeometry(tile_n, 1, gn_cpg, 0, 0)
+    # tickets of the last-block reduction (vps_conv_desc.tile_counter): an upper bound of the tile count of every kernel family
+    tickets = layer.nclass * (layer.cout_pad // tile_n) * max(mtiles, N * ((Qh + 7) // 8) * ((Qw + 15) // 16))
+    return ConvGeometry(tile_n, ksplit, gn_cpg, ksplit * layer.nclass * M * layer.cout_pad, tickets)
+
+
 class PackedConv:
     """One conv / transposed conv / linear / deformable conv of the path, packed for vps_conv2d.
 
@@ -315,54 +375,41 @@ class PackedConv:
     def __init__(self, weight, bias=None, bn=None, stride=1, padding=0, act=hip.ACT_NONE, slope=0.1,
                  transposed=False, deform=False, device='cuda', prec=None, _twin=False):
         w = weight.detach().float().cpu()
-        self.prec = DEFAULT_PREC if prec is None else prec
-        nout = w.shape[1] if transposed else w.shape[0]
+        prec = DEFAULT_PREC if prec is None else prec
         # narrow outputs (predict_flow, the 2-channel flow up-convolutions, 3-channel heads) run on the exact-fp32 vector kernel in
         # every mode - except where the matrix cores win although 30 of the 32 output columns of their tile are padding: 3x3 layers
         # with >= 64 input channels on >= 100 000 pixels (measured per layer, profiles/r03_conv_table_small_on_mfma.txt: predict_flow2
         # 194->2 @256x512 0.133 -> 0.080 ms per call; the low-resolution ones are faster on the vector kernel). Such a layer is
         # packed both ways and `__call__` picks by the size of the map.
-        nin = w.shape[0] if transposed else w.shape[1]
-        self.small = nout <= 4 and not deform and not _twin
-        self._mfma_twin = None
-        if self.small and SMALL_ON_MFMA and not transposed and w.shape[2] == 3 and nin >= 64 and (DEFAULT_PREC if prec is None else prec) != hip.PREC_F32:
-            self._mfma_twin = PackedConv(weight, bias, bn, stride, padding, act, slope, transposed, deform, device, prec, _twin=True)
-        if self.small:
-            self.prec = hip.PREC_F32
-        self.stride = stride
-        self.act, self.slope = act, float(slope)
-        self.deform = deform
-        self.transposed = transposed
+        nin, nout = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
+        small = nout <= 4 and not deform and not _twin
+        twin = None
+        if small and SMALL_ON_MFMA and not transposed and w.shape[2] == 3 and nin >= 64 and prec != hip.PREC_F32:
+            twin = PackedConv(weight, bias, bn, stride, padding, act, slope, transposed, deform, device, prec, _twin=True)
+        if small:
+            prec = hip.PREC_F32
+        cin_pad = _ceil(nin, 4)
+        kh, kw = (w.shape[2] // 2, w.shape[3] // 2) if transposed else w.shape[2:]       # (transposed: taps per output parity class)
+        korder = 1 if (cin_pad >= 64 or cin_pad % 32 == 0) and kh * kw > 1 else 0
         if not transposed:
-            O, I, kh, kw = w.shape
-            self.nclass, self.os = 1, 1
-            self.KH, self.KW = kh, kw
-            self.pad_y = (padding, padding)
-            self.pad_x = (padding, padding)
-            cin_pad = _ceil(I, 4)
-            self.korder = 1 if (cin_pad >= 64 or cin_pad % 32 == 0) and kh * kw > 1 else 0
-            if deform and self.korder == 0 and self.prec != hip.PREC_F32:
+            O, I = w.shape[:2]
+            pads = (padding, padding)
+            if deform and korder == 0:
                 # a deformable layer with few input channels (tap-major k order; none on the path): the split-operand kernels take
                 # deformable layers in the chunk-major order only - such a layer runs on the exact-fp32 kernel (vps_conv2d, VPS_EARG 17)
-                self.prec = hip.PREC_F32
-            blocks = [self._pack_taps(w.permute(0, 2, 3, 1).reshape(O, kh * kw, I), cin_pad)]
+                prec = hip.PREC_F32
+            blocks = [_pack_taps(w.permute(0, 2, 3, 1).reshape(O, kh * kw, I), cin_pad, korder)]
         else:
-            I, O, kh, kw = w.shape
-            assert stride == 2 and kh == kw and kh % 2 == 0, 'only stride-2 even-kernel transposed convs are on the path'
-            self.nclass, self.os = 4, 2
-            self.stride = 1
-            kc = kh // 2
-            self.KH = self.KW = kc
-            cin_pad = _ceil(I, 4)
+            I, O = w.shape[:2]
+            assert stride == 2 and w.shape[2] == w.shape[3] and w.shape[2] % 2 == 0, 'only stride-2 even-kernel transposed convs are on the path'
+            stride, kc = 1, kh                              # four stride-1 convolutions, one per output parity class
             pads, taps = [], []
             for par in range(2):
                 r = (par + padding) & 1
                 d = (par + padding - r) // 2
                 pads.append((kc - 1) - d)
                 taps.append([r + 2 * ((kc - 1) - u) for u in range(kc)])  # kernel index used by tap u
-            self.pad_y = tuple(pads)
-            self.pad_x = tuple(pads)
-            self.korder = 1 if (cin_pad >= 64 or cin_pad % 32 == 0) and kc * kc > 1 else 0
+            pads = tuple(pads)
             blocks = []
             for py in range(2):
                 for px in range(2):
@@ -370,46 +417,60 @@ class PackedConv:
                     for uy in range(kc):
                         for ux in range(kc):
                             wp[:, uy * kc + ux, :] = w[:, :, taps[py][uy], taps[px][ux]].t()
-                    blocks.append(self._pack_taps(wp, cin_pad))
-        self.cin, self.cin_pad, self.cout = I, cin_pad, O
-        self.tile_n = _tile_n(O)
-        self.cout_pad = _ceil(O, self.tile_n)
+                    blocks.append(_pack_taps(wp, cin_pad, korder))
         K = blocks[0].shape[1]
-        self.kpad = _ceil(K, 32)
-        packed = torch.zeros(self.nclass, self.cout_pad, self.kpad)
+        packed = torch.zeros(len(blocks), _ceil(O, _tile_n(O)), _ceil(K, 32))
         for c, b in enumerate(blocks):
             packed[c, :O, :K] = b
+        self._init(packed, device, prec, I, O, KH=kh, KW=kw, stride=stride, pads=pads, korder=korder, transposed=transposed, deform=deform,
+                   act=act, slope=slope, small=small, twin=twin, bias=bias, bn=bn, persistent=True)
+
+    @classmethod
+    def from_matrix(cls, mat, prec=None):
+        """GEMM against a device matrix mat [M, D] (rows = output channels) without a host round trip: out = x @ mat^T."""
+        M, D = mat.shape
+        assert D % 32 == 0
+        self = cls.__new__(cls)
+        w = torch.zeros(1, _ceil(M, _tile_n(M)), D, dtype=torch.float32, device=mat.device)
+        w[0, :M] = mat
+        self._init(w, mat.device, DEFAULT_PREC if prec is None else prec, D, M)
+        return self
+
+    def _init(self, packed, device, prec, cin, cout, *, KH=1, KW=1, stride=1, pads=(0, 0), korder=0, transposed=False, deform=False,
+              act=hip.ACT_NONE, slope=0.1, small=False, twin=None, bias=None, bn=None, persistent=False):
+        """every attribute of a layer. packed: fp32 [nclass][cout_pad][kpad] in the kernel's k order, on the host or the device.
+        persistent: it lives as long as the model - in f16x3 it owns a status slot and can fall back to bf16x6 (the others share slot 0)"""
+        self.prec, self.small, self._mfma_twin = prec, small, twin
+        self.stride, self.act, self.slope, self.deform, self.transposed = stride, act, float(slope), deform, transposed
+        self.nclass, self.os = (4, 2) if transposed else (1, 1)
+        self.KH, self.KW, self.pad_y, self.pad_x, self.korder = KH, KW, pads, pads, korder
+        self.cin, self.cin_pad, self.cout = cin, _ceil(cin, 4), cout
+        self.tile_n, self.cout_pad, self.kpad = _tile_n(cout), packed.shape[1], packed.shape[2]
+        self.gn_fused, self._launches = False, {}
         wscale = self._set_weights(packed, device)
-        self._fb = None
-        self.f16_slot = 0
-        if self.prec == hip.PREC_F16X3:
-            # what `use_fallback` needs to re-pack this layer for bf16x6: the fp32 weights in packed layout (host) — the epilogue
-            # scale without the f16x3 pre-scaling is restored below
+        # epilogue: y = acc*scale + shift
+        scale = None
+        shift = None if bias is None else bias.detach().float().cpu().clone()
+        if bn is not None:
+            g = bn['weight'].detach().float().cpu(); b = bn['bias'].detach().float().cpu()
+            m = bn['running_mean'].detach().float().cpu(); v = bn['running_var'].detach().float().cpu()
+            scale = g / torch.sqrt(v + bn.get('eps', 1e-5))
+            shift = ((torch.zeros(cout) if shift is None else shift) - m) * scale + b
+        self._fb, self.f16_slot = None, 0
+        if persistent and self.prec == hip.PREC_F16X3:
             self.f16_slot = _F16_NEXT[0] if _F16_NEXT[0] < F16_SLOTS - 1 else 0        # (the last slot is the correlations')
             if self.f16_slot:
                 _F16_NEXT[0] += 1
                 _F16_LAYERS[self.f16_slot] = weakref.ref(self)
-                self._fb = dict(packed=packed)
-        # epilogue: y = acc*scale + shift
-        scale = torch.ones(O)
-        shift = torch.zeros(O) if bias is None else bias.detach().float().cpu().clone()
-        if bn is not None:
-            g = bn['weight'].detach().float().cpu(); b = bn['bias'].detach().float().cpu()
-            m = bn['running_mean'].detach().float().cpu(); v = bn['running_var'].detach().float().cpu()
-            s = g / torch.sqrt(v + bn.get('eps', 1e-5))
-            shift = (shift - m) * s + b
-            scale = s
-            self.has_scale = True
-        else:
-            self.has_scale = False
-        if self._fb is not None:
-            self._fb.update(scale=scale.clone() if self.has_scale else None, has_scale=self.has_scale)
+                # what `use_fallback` needs to re-pack this layer for bf16x6: the fp32 weights in packed layout (host) and the
+                # epilogue scale without the f16x3 pre-scaling
+                self._fb = dict(packed=packed, scale=None if scale is None else scale.clone())
         if wscale is not None:
             # f16x3: the weights were pre-scaled per output channel by a power of two; undone exactly here
-            scale = scale * wscale[:O].cpu()
-            self.has_scale = True
-        self.scale = scale.to(device) if self.has_scale else None
-        self.shift = shift.to(device) if (bias is not None or bn is not None) else None
+            scale = wscale[:cout].contiguous() if scale is None else scale * wscale[:cout].cpu()
+        self.has_scale = scale is not None
+        self.scale = None if scale is None else scale.to(device)
+        self.shift = None if shift is None else shift.to(device)
 
     def use_fallback(self, device):
         """f16x3 -> bf16x6 for this layer, for good (an activation beyond the fp16 range was staged here). -> 1 if switched"""
@@ -418,28 +479,21 @@ class PackedConv:
         fb, self._fb = self._fb, None
         self.prec = hip.PREC_BF16X6
         self._set_weights(fb['packed'], device)
-        self.has_scale = fb['has_scale']
-        self.scale = fb['scale'].to(device) if fb['has_scale'] else None
-        self.__dict__.pop('_dcache', None)
+        self.scale = None if fb['scale'] is None else fb['scale'].to(device)
+        self.has_scale = self.scale is not None
+        self.forget_launches()
         return 1
 
-    def _pack_taps(self, wt, cin_pad):
-        """wt [O, ntap, I] -> [O, K] in the kernel's k order (see vps_conv_desc.korder)"""
-        O, ntap, I = wt.shape
-        if self.korder == 0:                                   # tap-major: k = tap*cin_pad + ci
-            wp = torch.zeros(O, ntap, cin_pad)
-            wp[..., :I] = wt
-            return wp.reshape(O, ntap * cin_pad)
-        nch = (cin_pad + 31) // 32                             # chunk-major: k = (chunk*ntap + tap)*32 + c
-        wp = torch.zeros(O, ntap, nch * 32)
-        wp[..., :I] = wt
-        return wp.view(O, ntap, nch, 32).permute(0, 2, 1, 3).reshape(O, nch * ntap * 32)
+    def forget_launches(self):
+        """drop the cached descriptors (after a change of the layer, or of a module-level switch that the geometry reads)"""
+        self._launches.clear()
 
     def _set_weights(self, packed, device):
         """packed fp32 [nclass][cout_pad][kpad] (host or device) -> the operand format of the selected arithmetic.
         Returns None, or (f16x3) the per-output-channel factor [cout_pad] the epilogue scale has to be multiplied with."""
+        self.w, self.w_split, self.w_thin = None, None, None
         if self.prec == hip.PREC_F32:
-            self.w, self.w_split = packed.to(device), None
+            self.w = packed.to(device)
             return None
         planes, r = [], packed.to(device)
         wscale = None
@@ -461,7 +515,6 @@ class PackedConv:
                 planes.append(h)
                 r = r - h.float()
         ws = torch.stack(planes, 0)                     # [planes][class][cout_pad][kpad]
-        self.w_thin = None
         if (THIN_KERNEL and self.prec == hip.PREC_F16X3 and not self.deform and not self.transposed and self.korder == 0 and self.KH == self.KW
                 and self.KH in (3, 7) and self.cin_pad in (4, 8, 12) and self.cout_pad == 64 and self.tile_n == 64):
             self.w_thin = pack_thin(ws[:2, 0], self.KH, self.cin_pad)
@@ -471,33 +524,8 @@ class PackedConv:
             # [plane][class][cout_pad/32][kpad/16][lane = 32*(k/8 % 2) + cout % 32][8 consecutive k]
             P, C, O, K = ws.shape
             ws = ws.view(P, C, O // 32, 32, K // 16, 2, 8).permute(0, 1, 2, 4, 5, 3, 6)
-        self.w, self.w_split = None, ws.contiguous()
+        self.w_split = ws.contiguous()
         return wscale
-
-    @classmethod
-    def from_matrix(cls, mat, prec=None):
-        """GEMM against a device matrix mat [M, D] (rows = output channels) without a host round trip: out = x @ mat^T."""
-        M, D = mat.shape
-        assert D % 32 == 0
-        self = cls.__new__(cls)
-        self.stride, self.act, self.slope, self.deform, self.transposed = 1, hip.ACT_NONE, 0.1, False, False
-        self.nclass, self.os, self.KH, self.KW = 1, 1, 1, 1
-        self.pad_y = self.pad_x = (0, 0)
-        self.cin = self.cin_pad = self.kpad = D
-        self.korder = 0
-        self.small = False
-        self.cout = M
-        self.tile_n = _tile_n(M)
-        self.cout_pad = _ceil(M, self.tile_n)
-        w = torch.zeros(1, self.cout_pad, D, dtype=torch.float32, device=mat.device)
-        w[0, :M] = mat
-        self.prec = DEFAULT_PREC if prec is None else prec
-        self._fb, self.f16_slot = None, 0
-        wscale = self._set_weights(w, mat.device)
-        self.scale, self.shift, self.has_scale = None, None, False
-        if wscale is not None:
-            self.scale, self.has_scale = wscale[:M].contiguous(), True
-        return self
 
     def out_hw(self, H, W):
         if self.transposed:
@@ -511,7 +539,7 @@ class PackedConv:
         gn = (stats, G): float64 tensor [GN_REP, 2*G] of zeros that receives the GroupNorm sums of the output from the epilogue
         (vps_conv_desc.gn_stats; deformable layers of the split-operand modes). `self.gn_fused` tells whether the launch took
         them (it does not when the layer is split over K) - the caller then runs the statistics pass itself."""
-        if getattr(self, '_mfma_twin', None) is not None and x.N * x.H * x.W >= 100000:
+        if self._mfma_twin is not None and x.N * x.H * x.W >= 100000:
             return self._mfma_twin(x, out, ws, name, res, res_shift, offset, act, gn, temp, keep)
         assert x.C == self.cin or (x.C >= self.cin and x.C <= self.cin_pad), (x.C, self.cin)
         assert x.coff % 4 == 0 and x.ld % 4 == 0 and x.coff + self.cin_pad <= x.ld, (x.coff, x.ld, self.cin_pad)
@@ -522,116 +550,93 @@ class PackedConv:
         # The workspace is persistent, so a layer sees the same operand addresses every frame: the filled descriptor (and the
         # split-K scratch it points to) is cached per operand set; a hit costs one dict lookup + the launch instead of ~50
         # ctypes field stores (the low-resolution layers run for 10-20 us, less than it takes to describe them).
-        ckey = (x.t.data_ptr(), x.N, x.H, x.W, x.ld, x.coff, out.t.data_ptr(), out.ld, out.coff,
-                None if res is None else (res.t.data_ptr(), res.ld, res.coff, res_shift),
-                None if offset is None else (offset.t.data_ptr(), offset.ld), act, getattr(hip.stream_ptr(), 'value', None) or 0,
-                None if gn is None else (gn[0].data_ptr(), gn[1]))
-        cache = self.__dict__.setdefault('_dcache', {})
-        hit = cache.get(ckey)
+        key = (x.t.data_ptr(), x.N, x.H, x.W, x.ld, x.coff, out.t.data_ptr(), out.ld, out.coff,
+               None if res is None else (res.t.data_ptr(), res.ld, res.coff, res_shift),
+               None if offset is None else (offset.t.data_ptr(), offset.ld), act, _stream_key(),
+               None if gn is None else (gn[0].data_ptr(), gn[1]))
+        hit = self._launches.get(key)
         if hit is not None and CONV_TRACE is None:
-            self.gn_fused = bool(hit[0].gn_stats)
-            hip.conv2d(hit[0])
+            d = hit.desc
+            self.gn_fused = bool(d.gn_stats)
+            hip.conv2d(d)
             return out
+        Qh, Qw = (x.H, x.W) if self.transposed else (Ho, Wo)
+        geo = conv_geometry(self, x.N, Qh, Qw, out.ld, out.coff, res is not None, None if gn is None else gn[1])
+        d = self._describe(x, out, Qh, Qw, res, res_shift, offset, act, gn, geo)
+        scratch = self._scratch(d, geo, ws, x.t.device)
+        self.gn_fused = geo.gn_cpg > 0
+        self._launch(d, x, res is not None)
+        if len(self._launches) >= 16:
+            self._launches.clear()
+        self._launches[key] = _Launch(d, (scratch, x.t, out.t, None if res is None else res.t, None if offset is None else offset.t))
+        return out
+
+    def _describe(self, x, out, Qh, Qw, res, res_shift, offset, act, gn, geo):
+        """-> the vps_conv_desc of this layer on these operands with the geometry `geo` (all but the split-K scratch: `_scratch`)"""
         d = hip.ConvDesc()
         d.inp = x.t.data_ptr(); d.N, d.H, d.W = x.N, x.H, x.W
         d.in_ld, d.in_coff, d.cin_pad = x.ld, x.coff, self.cin_pad
-        d.prec = self.prec
-        d.korder = self.korder
+        d.prec, d.korder = self.prec, self.korder
         if self.prec == hip.PREC_F32:
             d.w = self.w.data_ptr()
         else:
             d.w_split = self.w_split.data_ptr()
-            if getattr(self, 'w_thin', None) is not None and self.prec == hip.PREC_F16X3:
+            if self.w_thin is not None:
                 d.w_thin = self.w_thin.data_ptr()
+        if self.prec == hip.PREC_F16X3:
+            d.status = f16_status(x.t.device).data_ptr() + 4 * self.f16_slot
         d.cout, d.cout_pad, d.kpad = self.cout, self.cout_pad, self.kpad
         d.KH, d.KW, d.stride = self.KH, self.KW, self.stride
         d.pad_y[0], d.pad_y[1] = self.pad_y; d.pad_x[0], d.pad_x[1] = self.pad_x
-        d.out = out.t.data_ptr(); d.Ho, d.Wo, d.out_ld, d.out_coff = Ho, Wo, out.ld, out.coff
-        if self.transposed:
-            d.Qh, d.Qw, d.os_y, d.os_x, d.nclass = x.H, x.W, 2, 2, 4
-        else:
-            d.Qh, d.Qw, d.os_y, d.os_x, d.nclass = Ho, Wo, 1, 1, 1
+        d.out = out.t.data_ptr(); d.Ho, d.Wo, d.out_ld, d.out_coff = out.H, out.W, out.ld, out.coff
+        d.Qh, d.Qw, d.os_y, d.os_x, d.nclass = Qh, Qw, self.os, self.os, self.nclass
         d.scale = self.scale.data_ptr() if self.scale is not None else None
         d.shift = self.shift.data_ptr() if self.shift is not None else None
         if res is not None:
             d.res = res.t.data_ptr(); d.res_ld, d.res_coff, d.res_shift = res.ld, res.coff, res_shift
-            assert res.C == self.cout and res.H == (Ho >> res_shift) and res.W == (Wo >> res_shift)
-        d.act = self.act if act is None else act
-        d.slope = self.slope
+            assert res.C == self.cout and res.H == (out.H >> res_shift) and res.W == (out.W >> res_shift)
+        d.act, d.slope = self.act if act is None else act, self.slope
         if self.deform:
             assert offset is not None and offset.coff == 0 and offset.C >= 2 * self.KH * self.KW
             d.offset = offset.t.data_ptr(); d.off_ld = offset.ld
-        d.tile_n = self.tile_n
-        M = x.N * d.Qh * d.Qw
-        # deformable layers with a multiple of 256 output channels on the large maps: one block computes all 256 columns of its
-        # 128 pixels, so the bilinear loader runs once per pixel tile instead of once per 128 columns (conv_mfma.hip, tile_n 256)
-        wide = (DCN256[0] and self.deform and self.prec == hip.PREC_F16X3 and self.korder == 1 and self.cout_pad % 256 == 0
-                and (M + 127) // 128 * (self.cout_pad // 256) >= DCN256_MIN_TILES)
-        tile_n = 256 if wide else self.tile_n
-        d.tile_n = tile_n
-        if self.prec == hip.PREC_F16X3:
-            d.status = f16_status(x.t.device).data_ptr() + 4 * getattr(self, 'f16_slot', 0)
-        # split-K for launches that cannot fill 256 CUs
-        tiles = ((M + 127) // 128) * (self.cout_pad // tile_n) * d.nclass
-        ksteps = self.kpad // 32
-        ksplit = 1
-        if tiles < 256 and ksteps >= 8 and not getattr(self, 'small', False):
-            ksplit = max(1, min((SPLITK_TARGET_BLOCKS + tiles - 1) // tiles, ksteps // 4, 32))
-            ntap = self.KH * self.KW
-            if self.korder == 1:
-                # chunk-major layers split over whole 32-channel chunks (vps_conv2d: `chunk_split`); the ranges may be uneven (the last
-                # split is shorter) - the largest count <= target that ceil-division of the chunk count reproduces
-                nch = ksteps // ntap
-                ksplit = max(k for k in range(1, ksplit + 1) if -(-nch // -(-nch // k)) == k)
-            else:
-                per = (ksteps + ksplit - 1) // ksplit
-                ksplit = (ksteps + per - 1) // per
-        d.ksplit = ksplit
-        self.gn_fused = False
-        if gn is not None and self.deform and self.prec != hip.PREC_F32 and ksplit == 1 and res is None and not ((self.cout | out.ld | out.coff) & 3):
-            cpg = self.cout // gn[1]
-            if self.cout % gn[1] == 0 and (cpg == 4 or cpg % 8 == 0):
-                assert gn[0].dtype == torch.float64 and gn[0].numel() == GN_REP * 2 * gn[1] and gn[0].is_contiguous()
-                d.gn_stats, d.gn_cpg, d.gn_rep = gn[0].data_ptr(), cpg, GN_REP
-                self.gn_fused = True
-        if ksplit > 1:
-            need = ksplit * d.nclass * M * self.cout_pad
-            # tickets of the last-block reduction (vps_conv_desc.tile_counter): an upper bound of the tile count of every kernel family
-            ntick = d.nclass * (self.cout_pad // tile_n) * max((M + 127) // 128, x.N * ((d.Qh + 7) // 8) * ((d.Qw + 15) // 16))
-            if ws is not None:
-                # one scratch buffer per stream: branches of the frame graph that run concurrently must not share it
-                key = '__splitk_ws_%x' % (getattr(hip.stream_ptr(), 'value', None) or 0)
-                wsb = ws.bufs.get(key)
-                if wsb is None or wsb.numel() < need:
-                    wsb = torch.empty(max(need, 1 << 24), dtype=torch.float32, device=x.t.device)
-                    ws.bufs[key] = wsb
-                tck = ws.bufs.get(key + '_tickets')
-                if tck is None or tck.numel() < ntick:
-                    tck = torch.zeros(max(ntick, 1 << 16), dtype=torch.int32, device=x.t.device)     # zero once: launches leave them zero
-                    ws.bufs[key + '_tickets'] = tck
-            else:
-                wsb = torch.empty(need, dtype=torch.float32, device=x.t.device)
-                tck = torch.zeros(ntick, dtype=torch.int32, device=x.t.device)
-            d.ws = wsb.data_ptr()
-            if SPLITK_LAST_BLOCK:
-                d.tile_counter = tck.data_ptr()
-            self._last_ws = (wsb, tck)  # keep alive until the next call
-        if CONV_TRACE is not None:
-            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-            hip.conv2d(d)
-            e1.record()
-            CONV_TRACE.append((self.flops(x.N, x.H, x.W), e0, e1,
-                               '%d->%d k%dx%d s%d %s%s n%d %dx%d tile%d ksplit%d p%d' % (self.cin, self.cout, self.KH, self.KW, self.stride,
-                                                                                   'T' if self.transposed else '', 'D' if self.deform else '',
-                                                                                   x.N, x.H, x.W, tile_n, ksplit, self.prec),
-                               self.bytes(x.N, x.H, x.W, res is not None)))
+        d.tile_n, d.ksplit = geo.tile_n, geo.ksplit
+        if geo.gn_cpg:
+            assert gn[0].dtype == torch.float64 and gn[0].numel() == GN_REP * 2 * gn[1] and gn[0].is_contiguous()
+            d.gn_stats, d.gn_cpg, d.gn_rep = gn[0].data_ptr(), geo.gn_cpg, GN_REP
+        return d
+
+    def _scratch(self, d, geo, ws, device):
+        """point a split-K launch at its partial-sum scratch and tickets -> the two tensors (None if the launch is not split)"""
+        if geo.ksplit == 1:
+            return None
+        if ws is not None:
+            # one scratch buffer per stream: branches of the frame graph that run concurrently must not share it
+            key = '__splitk_ws_%x' % _stream_key()
+            wsb = ws.bufs.get(key)
+            if wsb is None or wsb.numel() < geo.scratch_floats:
+                wsb = ws.bufs[key] = torch.empty(max(geo.scratch_floats, 1 << 24), dtype=torch.float32, device=device)
+            tck = ws.bufs.get(key + '_tickets')
+            if tck is None or tck.numel() < geo.tickets:
+                tck = ws.bufs[key + '_tickets'] = torch.zeros(max(geo.tickets, 1 << 16), dtype=torch.int32, device=device)     # zero once: launches leave them zero
         else:
-            hip.conv2d(d)
-        if len(cache) >= 16:
-            cache.clear()
-        cache[ckey] = (d, wsb if ksplit > 1 else None, x.t, out.t, None if res is None else res.t, None if offset is None else offset.t)
-        return out
+            wsb = torch.empty(geo.scratch_floats, dtype=torch.float32, device=device)
+            tck = torch.zeros(geo.tickets, dtype=torch.int32, device=device)
+        d.ws = wsb.data_ptr()
+        if SPLITK_LAST_BLOCK:
+            d.tile_counter = tck.data_ptr()
+        return wsb, tck
+
+    def _launch(self, d, x, has_res):
+        """vps_conv2d, timed with HIP events into CONV_TRACE if bench.py asked for it"""
+        if CONV_TRACE is None:
+            return hip.conv2d(d)
+        e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        hip.conv2d(d)
+        e1.record()
+        tag = '%d->%d k%dx%d s%d %s%s n%d %dx%d tile%d ksplit%d p%d' % (self.cin, self.cout, self.KH, self.KW, self.stride, 'T' if self.transposed else '',
+                                                                        'D' if self.deform else '', x.N, x.H, x.W, d.tile_n, d.ksplit, self.prec)
+        CONV_TRACE.append((self.flops(x.N, x.H, x.W), e0, e1, tag, self.bytes(x.N, x.H, x.W, has_res)))
 
     def bytes(self, x_N, x_H, x_W, has_res=False):
         """algorithmic HBM bytes of one call: every input / weight / residual element read once, every output written once."""
