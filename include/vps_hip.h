@@ -371,6 +371,27 @@ int vps_panoptic_combine_dev(const float* fcn_score, int score_ld, int Hs, int W
 int vps_png_info(const uint8_t* file, int64_t nbytes, int32_t* H, int32_t* W, int32_t* channels);
 int vps_png_decode_bgr8(const uint8_t* file, int64_t nbytes, uint8_t* out, int64_t out_capacity);
 
+/* PNG input with the un-filter on the DEVICE (opt-in: `ClipFeeder(png='device')`; csrc/png_in_ops.hip). The zlib stream is inflated on the
+ * HOST (one function, no device work, no stream, no interpreter lock, no allocation); the five scanline filters and the RGB -> BGR copy
+ * run on the device and give vps_png_decode_bgr8's bytes.
+ * vps_png_inflate: takes the files vps_png_decode_bgr8 takes, makes its checks and returns its error codes; scan receives the FILTERED
+ * scanlines as zlib delivers them, H rows of 1 + W*channels bytes, tightly packed, each led by its filter byte; scan_capacity in bytes
+ * >= H * (1 + W*channels). The stream is inflated straight into scan (a pinned staging slot). Every filter byte is checked to be 0..4
+ * here - the device never sees another value.
+ * vps_png_reconstruct_ws (HOST arithmetic only): the workspace bytes of vps_png_reconstruct.
+ * vps_png_reconstruct: every pointer is a DEVICE pointer (scan and out_bgr at any byte address, ws 4-byte aligned); launches on
+ * `stream`, no sync, no hidden allocation. scan is READ in aligned 4-byte words: where scan or scan + H*(1 + W*channels) is not a
+ * multiple of 4, up to 3 bytes in front of the first row and behind the last row are loaded (and ignored) - they share an aligned word
+ * with a byte of the buffer, so the read cannot leave its page, but it is outside the caller's H*(1 + W*channels) bytes. scan as vps_png_inflate wrote it, H / W / channels (1, 3 or 4) as vps_png_info reported
+ * them; out_bgr = uint8 [H][W][3] BGR (alpha dropped, grey replicated), out_capacity >= H*W*3 bytes. A row of type None or Sub
+ * (and row 0) starts a group of rows that reads nothing above it; one workgroup rebuilds one group as a skewed wavefront, in bands of
+ * vps_png_reconstruct_block_rows() rows (a constant of the build; HOST, no device work), and no workgroup waits for another. */
+int vps_png_inflate(const uint8_t* file, int64_t nbytes, uint8_t* scan, int64_t scan_capacity);
+int vps_png_reconstruct_ws(int H, int W, int channels, int64_t* ws_bytes);
+int vps_png_reconstruct(const uint8_t* scan, int H, int W, int channels, uint8_t* out_bgr, int64_t out_capacity,
+                        void* ws, int64_t ws_bytes, void* stream);
+int vps_png_reconstruct_block_rows(void);
+
 /* JPEG input (the VIPER frames). The Huffman bit stream is decoded on the HOST (two functions, no device work, no stream, no
  * interpreter lock, no allocation); dequantisation, the 8x8 inverse DCT, chroma upsampling and YCbCr -> BGR run on the DEVICE and are
  * bit-exact with libjpeg's default decode (slow-integer IDCT, fancy upsampling, 16-bit fixed-point colour) - what cv2.imread and PIL

@@ -21,6 +21,17 @@ events (median of 30 launches) beside its 12.5 MB of algorithmic traffic at 8 TB
 consumer. The gain of the native path is host CPU time and pinned pixel semantics; the device stage is microseconds off the model's
 critical path.
 
+    python tools/bench_input_pipeline.py --png-device [--frames 16] [--workers 1 2 4 8 16] [--out FILE]
+
+PNG-DEVICE mode (`ClipFeeder(png='device')`: the worker only inflates, the device un-filters): on the same PIL-written 1024x2048 RGB
+frames it times, per worker count and alternating in one run, the two host legs of a feeder worker - `decode` (`vps_png_decode_bgr8`:
+inflate + un-filter + BGR copy into a reused staging buffer) and `inflate` (`vps_png_inflate` alone) - and reports their single-thread
+ms per frame (the difference is what the host stops paying), the filter-type histogram and the longest row group of the files, with a
+GPU `vps_png_reconstruct` by events (median of 30 launches on an idle device), and a `ClipFeeder` drained by an otherwise idle consumer
+with png='host' and png='device' at equal thread counts (`--feeder-frames` frames timed in steady state). `--clip` adds the PNG-fed
+detector clip of `bench.py --full` (its `from_png` extra) with png='host' against png='device', alternating. `--parent-lib FILE`: a shared library built from another commit's
+csrc/png_host.cpp, whose `vps_png_decode_bgr8` is timed beside this tree's.
+
 NODE mode (round 6): what the host of an 8-GPU node has to deliver - `--node` decoder PROCESSES (one per rank, as
 `bench.py --gpus 8` starts them), each with the thread budget of a rank's `ClipFeeder` (`--threads`, default 6) and pinned to its own
 block of cores (os.sched_setaffinity: cores [r * C/8, (r+1) * C/8) - a rank's decode threads stay on the cores next to its GPU and
@@ -203,6 +214,184 @@ def jpeg_mode(args):
     print(line)
 
 
+def detector_clip(args, files, dev):
+    """the PNG-fed clip of `bench.py --full` (its `from_png` extra: ClipShardRunner.run(ClipFeeder(...)) over 32 frames of 8 PIL-written files,
+    --png-workers decode threads, the pool given 0.2 s to fill its window) with png='host' - the parent commit's path, byte for byte - against
+    png='device', alternating in one process; the README states a box-to-box spread of +-1.5 % for the clip rate"""
+    import torch
+    import vps_amd
+    from vps_amd import nhwc, synth
+    from vps_amd.clip_shard import ClipShardRunner, DetectorBackend
+    from vps_amd.pipeline import ClipFeeder, DeviceImagePrep
+    nhwc.DEFAULT_PREC = nhwc.PREC_NAMES[args.prec]
+    H, W = args.height, args.width
+    cfg = vps_amd.Config.fromfile(os.path.join(ROOT, 'configs', 'cityscapes', 'fusetrack.py'))
+    model = vps_amd.build_detector(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)
+    synth.load_synth(model, 0)
+    runner = ClipShardRunner(DetectorBackend(model, H, W, prefetch=True), 0, 1, None, dev)
+
+    def reset():
+        model._cache = None; model._handoff = None; model._pf = None
+        model.reset_tracker()
+    prep = DeviceImagePrep(**cfg.img_norm_cfg, size_divisor=32, img_scale=(max(H, W), min(H, W)), device=dev)
+    names, nfr = files[:8], 32
+    rates = {'host': [], 'device': []}
+    vid = 20
+    for mode in ('host', 'device'):                                          # warm-up of both paths
+        reset()
+        runner.run(ClipFeeder([names[t % 8] for t in range(8)], prep, workers=args.png_workers, png=mode), 8, video_id=vid); vid += 1
+    for rnd in range(args.clip_rounds):
+        for mode in ('host', 'device'):
+            reset()
+            feeder = ClipFeeder([names[t % 8] for t in range(nfr)], prep, workers=args.png_workers, png=mode).start()
+            time.sleep(0.2)
+            torch.cuda.synchronize()
+            c0 = time.perf_counter()
+            runner.run(feeder, nfr, video_id=vid); vid += 1
+            torch.cuda.synchronize()
+            rates[mode].append(round(nfr / (time.perf_counter() - c0), 3))
+            feeder.close()
+            assert feeder.fallback_decodes == 0 and feeder.native_png_device == (nfr if mode == 'device' else 0)
+    reset()
+    med = {k: float(np.median(v)) for k, v in rates.items()}
+    ratio = med['device'] / med['host']
+    return dict(frames=nfr, decode_threads=args.png_workers, prec=args.prec, rounds_alternating=args.clip_rounds, frames_per_s=rates,
+                median_frames_per_s={k: round(v, 3) for k, v in med.items()}, device_over_host=round(ratio, 4),
+                yardstick="png=host is the parent commit's path (same decoder code, same bytes); stated box-to-box spread of the clip rate: +-1.5 %",
+                finding=('png=device is within the +-1.5 % spread of png=host' if abs(ratio - 1) <= 0.015 else
+                         'png=device is %.1f %% %s than png=host, beyond the +-1.5 %% spread: the reconstruct kernel %s' % (
+                             100 * abs(ratio - 1), 'slower' if ratio < 1 else 'faster',
+                             "disturbs the frame (it runs in order on the consumer's stream)" if ratio < 1 else 'does not hold the frame back')))
+
+
+def png_device_mode(args):
+    import ctypes
+    import threading
+    import torch
+    from PIL import Image
+    from vps_amd import hip, synth
+    from vps_amd.pipeline import ClipFeeder, DeviceImagePrep, png_inflate, png_reconstruct
+    H, W = args.height, args.width
+    tmp = tempfile.mkdtemp(prefix='vps_input_')
+    files = []
+    for t in range(args.frames):
+        fr = synth.synth_frame(H, W, seed=t % 4, shift=(2 * (t % 8), t % 8), noise=2.0).astype(np.uint8)
+        fn = os.path.join(tmp, 'f%04d_leftImg8bit.png' % t)
+        Image.fromarray(np.ascontiguousarray(fr[:, :, ::-1])).save(fn, compress_level=6)
+        files.append(fn)
+    lib = hip.load_host()
+    datas = [bytearray(open(f, 'rb').read()) for f in files]                 # the files sit in memory: the decoders are what is timed
+    cbufs = [(ctypes.c_char * len(d)).from_buffer(d) for d in datas]
+    scan0, pi = png_inflate(datas[0])
+    hist, longest = [0] * 5, 0
+    for d in datas[:8]:
+        types = png_inflate(d)[0].reshape(pi.H, 1 + pi.W * pi.C)[:, 0]
+        for k in range(5):
+            hist[k] += int((types == k).sum())
+        starts = np.flatnonzero((types < 2) | (np.arange(pi.H) == 0))
+        longest = max(longest, int(np.diff(np.append(starts, pi.H)).max()))
+    out = dict(mode='png-device', frames=args.frames, size=[H, W], channels=pi.C, png_MB_per_frame=round(sum(len(d) for d in datas) / 1e6 / len(datas), 2),
+               scan_MB_per_frame=round(pi.scan_bytes / 1e6, 2), host_cpus=os.cpu_count(),
+               filter_type_rows_of_8_files=dict(zip(('none', 'sub', 'up', 'average', 'paeth'), hist)), longest_row_group_of_8_files=longest,
+               legs='decode = vps_png_decode_bgr8 (inflate + un-filter + BGR copy), inflate = vps_png_inflate; both from memory into a reused '
+                    'per-thread staging buffer, as a ClipFeeder worker calls them')
+    legs = [('decode', lib.vps_png_decode_bgr8, H * W * 3), ('inflate', lib.vps_png_inflate, pi.scan_bytes)]
+    if args.parent_lib:
+        par = ctypes.CDLL(args.parent_lib)
+        par.vps_png_decode_bgr8.restype = ctypes.c_int
+        par.vps_png_decode_bgr8.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
+        legs.insert(0, ('parent_decode', par.vps_png_decode_bgr8, H * W * 3))
+    local = threading.local()
+
+    def leg(fn, nbytes):
+        def work(i):
+            if getattr(local, 'n', 0) < nbytes:
+                local.stage, local.n = np.empty(nbytes, dtype=np.uint8), nbytes
+            hip.check(fn(cbufs[i], len(datas[i]), local.stage.ctypes.data_as(ctypes.c_void_p), nbytes), 'png host leg')
+        return work
+    idx = list(range(len(datas)))
+    for name, _, _ in legs:
+        out[name + '_frames_per_s'] = {}
+    for nw in args.workers:
+        for rnd in range(2):                                                  # alternating; the second round is kept
+            for name, fn, nbytes in legs:
+                with ThreadPoolExecutor(nw) as ex:
+                    list(ex.map(leg(fn, nbytes), idx[:nw]))                   # warm-up: the threads' buffers
+                    t0 = time.perf_counter()
+                    list(ex.map(leg(fn, nbytes), idx))
+                    out[name + '_frames_per_s'][str(nw)] = round(len(idx) / (time.perf_counter() - t0), 1)
+    ms = {}
+    for rnd in range(3):                                                      # one thread, alternating, best of 3 passes over the files
+        for name, fn, nbytes in legs:
+            w = leg(fn, nbytes)
+            t0 = time.perf_counter()
+            for i in idx:
+                w(i)
+            ms[name] = min(ms.get(name, 1e9), 1e3 * (time.perf_counter() - t0) / len(idx))
+    out['one_thread_ms_per_frame'] = {k: round(v, 3) for k, v in ms.items()}
+    out['one_thread_unfilter_and_bgr_ms_per_frame'] = round(ms['decode'] - ms['inflate'], 3)
+    out['one_thread_unfilter_share_of_decode'] = round((ms['decode'] - ms['inflate']) / ms['decode'], 3)
+    if torch.cuda.is_available():
+        dev = torch.device('cuda:0')
+        scan = torch.from_numpy(scan0).to(dev)
+        need = ctypes.c_int64()
+        hip.check(hip.load().vps_png_reconstruct_ws(pi.H, pi.W, pi.C, ctypes.byref(need)), 'vps_png_reconstruct_ws')
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        for _ in range(5):
+            png_reconstruct(scan, pi.H, pi.W, pi.C, ws)
+        torch.cuda.synchronize()
+        t = []
+        for _ in range(30):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); png_reconstruct(scan, pi.H, pi.W, pi.C, ws); e1.record()
+            e1.synchronize()
+            t.append(e0.elapsed_time(e1))
+        out['reconstruct_ms_median_of_30'] = round(float(np.median(t)), 4)
+        out['reconstruct_ms_min_max'] = [round(min(t), 4), round(max(t), 4)]
+        out['reconstruct_block_rows'] = hip.png_block_rows()
+        prep = DeviceImagePrep(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True, size_divisor=32,
+                               img_scale=(max(H, W), min(H, W)), device=dev)
+        out['feeder_frames_per_s'] = {}
+        for nw in args.workers:
+            # steady state only: the read-ahead window is 2 x workers frames, so the clock starts after the first window + 1 frames have
+            # been consumed (the pool refills behind the consumer from then on) and stops `timed` frames later, with a full window of
+            # the clip still ahead - the window is as far ahead at the stop as at the start, and no frame decoded before the start counts
+            warm, timed = 2 * nw + 1, args.feeder_frames
+            clip = [files[k % len(files)] for k in range(warm + timed + 2 * nw + 2)]
+            res = {}
+            for rnd in range(2):                                              # alternating; the second round is kept
+                for mode in ('host', 'device'):
+                    fd = ClipFeeder(clip, prep, workers=nw, png=mode)
+                    for k in range(warm):
+                        fd(k)
+                    torch.cuda.synchronize()
+                    w0, u0 = fd.stats['wait_for_decode_s'], fd.stats['upload_prep_s']
+                    t0 = time.perf_counter()
+                    for k in range(warm, warm + timed):
+                        fd(k)
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                    n_dev = fd.native_png_device
+                    fd.close()
+                    assert fd.fallback_decodes == 0 and fd.out_of_window == 0 and n_dev == (warm + timed if mode == 'device' else 0)
+                    res[mode] = dict(frames_per_s=round(timed / dt, 1), wait_for_decode_s=round(fd.stats['wait_for_decode_s'] - w0, 4),
+                                     upload_prep_s=round(fd.stats['upload_prep_s'] - u0, 4))
+            out['feeder_frames_per_s'][str(nw)] = res
+        out['feeder_timed_frames'] = args.feeder_frames
+        out['feeder_note'] = ('consumer = fd(t) in a loop on an otherwise idle main thread (no detector beside it); steady state: the clock starts after '
+                              '2 x workers + 1 frames and stops with a full read-ahead window still to come')
+        if args.clip:
+            out['detector_clip'] = detector_clip(args, files, dev)
+    for f in files:
+        os.remove(f)
+    os.rmdir(tmp)
+    line = json.dumps(out)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(line + '\n')
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=48)
@@ -210,7 +399,15 @@ def main():
     ap.add_argument('--format', choices=['png', 'jpeg'], default='png', help='jpeg: native entropy decode against the PIL route, 1080x1920 frames')
     ap.add_argument('--height', type=int, default=None, help='default 1024 (png, Cityscapes-VPS) / 1080 (jpeg, VIPER)')
     ap.add_argument('--width', type=int, default=None, help='default 2048 (png) / 1920 (jpeg)')
-    ap.add_argument('--out', default=None, help='jpeg mode: also write the JSON line to this file')
+    ap.add_argument('--out', default=None, help='jpeg / png-device mode: also write the JSON line to this file')
+    ap.add_argument('--png-device', action='store_true', help="png: the host legs and the feeder with png='host' against png='device' (inflate on the "
+                    "worker, un-filter on the device), and vps_png_reconstruct by events")
+    ap.add_argument('--feeder-frames', type=int, default=96, help='png-device mode: frames timed per feeder run, in steady state')
+    ap.add_argument('--clip', action='store_true', help="png-device mode: also the PNG-fed detector clip of bench.py --full (32 frames) with png='host' against png='device'")
+    ap.add_argument('--clip-rounds', type=int, default=3)
+    ap.add_argument('--png-workers', type=int, default=6, help='--clip: decode threads, as bench.py --png-workers')
+    ap.add_argument('--prec', default='f16x3', choices=['f32', 'bf16x6', 'f16x3'], help='--clip: arithmetic of the detector, as bench.py --prec')
+    ap.add_argument('--parent-lib', default=None, help='png-device mode: a library with another build of vps_png_decode_bgr8, timed beside this one')
     ap.add_argument('--node', type=int, default=0, help='node mode: this many rank processes decode concurrently')
     ap.add_argument('--threads', type=int, default=6, help='node mode: decode threads per rank (ClipFeeder workers)')
     ap.add_argument('--seconds', type=float, default=8.0)
@@ -224,6 +421,8 @@ def main():
         return jpeg_mode(args)
     if args.node:
         return node_mode(args)
+    if args.png_device:
+        return png_device_mode(args)
     import torch
     from PIL import Image
     from vps_amd import synth

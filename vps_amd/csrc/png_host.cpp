@@ -5,6 +5,8 @@
 // ctypes runs WITHOUT the lock, so plain threads scale. Scope: what the datasets of the path contain - 8-bit, non-interlaced, colour
 // type 2 (RGB), 6 (RGBA, alpha dropped like cv2.IMREAD_COLOR) or 0 (grey, replicated); anything else returns VPS_EARG and the caller
 // falls back to its general decoder. Output: BGR uint8 [H][W][3] (cv2 / mmcv channel order). zlib does the inflate.
+// vps_png_inflate is the host half of the opt-in split (`ClipFeeder(png='device')`): the same files, checks and error codes, but the
+// filtered scanlines are left as zlib delivers them, in the caller's buffer, for vps_png_reconstruct (png_in_ops.hip) to un-filter.
 #include <zlib.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -96,23 +98,27 @@ extern "C" int vps_png_info(const uint8_t* file, int64_t nbytes, int32_t* H, int
     return 0;
 }
 
-extern "C" int vps_png_decode_bgr8(const uint8_t* file, int64_t nbytes, uint8_t* out, int64_t out_capacity) {
-    int32_t H, W, C;
-    const int st = vps_png_info(file, nbytes, &H, &W, &C);
+namespace {
+
+// what vps_png_decode_bgr8 and vps_png_inflate share: header, the size limit, the chunk walk and the inflate of the IDAT data into `raw`
+// (`need(total)` names the buffer once the header has sized it: the thread's scratch, or the caller's). On success raw holds H rows of
+// 1 + W*C bytes, each led by its filter byte, still filtered.
+struct PngGeom { int32_t H, W, C; size_t stride; };
+
+template <class Need>
+int inflate_idat(const uint8_t* file, int64_t nbytes, PngGeom* g, uint8_t** raw_out, Need need) {
+    const int st = vps_png_info(file, nbytes, &g->H, &g->W, &g->C);
     if (st) return st;
-    if (!out || out_capacity < (int64_t)H * W * 3) return VPS_EARG(4);
-    const size_t stride = (size_t)W * C;
-    // zlib counts the output space in a 32-bit uInt: an image whose raw size does not fit (a 65535 x 65535 header passes the checks
-    // above: ~17 GB) would be inflated only in part, with `avail_out == 0` reached early and uninitialised rows behind it.
-    // Refused: the caller falls back to the general decoder. 1 GiB is > 100 frames of the path's size.
-    if ((stride + 1) * (size_t)H > ((size_t)1 << 30)) return VPS_EARG(9);
-    uint8_t* raw = t_raw.get((stride + 1) * (size_t)H);                   // filter byte + pixels per scanline (the thread's buffer)
-    if (!raw) return VPS_EARG(5);
+    g->stride = (size_t)g->W * g->C;
+    const size_t total = (g->stride + 1) * (size_t)g->H;                  // filter byte + pixels per scanline
+    uint8_t* raw = nullptr;
+    const int sn = need(*g, total, &raw);
+    if (sn) return sn;
     z_stream zs;
     memset(&zs, 0, sizeof(zs));
     if (inflateInit(&zs) != Z_OK) return VPS_EARG(6);
     zs.next_out = raw;
-    zs.avail_out = (uInt)((stride + 1) * (size_t)H);
+    zs.avail_out = (uInt)total;
     int64_t pos = 8;
     int zret = Z_OK;
     bool end = false;
@@ -133,6 +139,45 @@ extern "C" int vps_png_decode_bgr8(const uint8_t* file, int64_t nbytes, uint8_t*
     const bool complete = zs.avail_out == 0 && (zret == Z_STREAM_END || zret == Z_OK);
     inflateEnd(&zs);
     if (!complete) return VPS_EARG(7);
+    *raw_out = raw;
+    return 0;
+}
+
+// zlib counts the output space in a 32-bit uInt: an image whose raw size does not fit (a 65535 x 65535 header passes the checks
+// of vps_png_info: ~17 GB) would be inflated only in part, with `avail_out == 0` reached early and uninitialised rows behind it.
+// Refused: the caller falls back to the general decoder. 1 GiB is > 100 frames of the path's size.
+inline bool too_large(size_t total) { return total > ((size_t)1 << 30); }
+
+}  // namespace
+
+extern "C" int vps_png_inflate(const uint8_t* file, int64_t nbytes, uint8_t* scan, int64_t scan_capacity) {
+    PngGeom g;
+    uint8_t* raw = nullptr;
+    const int st = inflate_idat(file, nbytes, &g, &raw, [&](const PngGeom&, size_t total, uint8_t** p) {
+        if (!scan || scan_capacity < 0 || (uint64_t)scan_capacity < total) return VPS_EARG(4);
+        if (too_large(total)) return VPS_EARG(9);
+        *p = scan;                                                       // straight into the caller's (pinned) buffer
+        return 0;
+    });
+    if (st) return st;
+    // the device stage never sees a filter type outside 0..4
+    for (int y = 0; y < g.H; ++y)
+        if (raw[(size_t)y * (g.stride + 1)] > 4) return VPS_EARG(8);
+    return 0;
+}
+
+extern "C" int vps_png_decode_bgr8(const uint8_t* file, int64_t nbytes, uint8_t* out, int64_t out_capacity) {
+    PngGeom g;
+    uint8_t* raw = nullptr;
+    const int st = inflate_idat(file, nbytes, &g, &raw, [&](const PngGeom& q, size_t total, uint8_t** p) {
+        if (!out || out_capacity < (int64_t)q.H * q.W * 3) return VPS_EARG(4);
+        if (too_large(total)) return VPS_EARG(9);
+        *p = t_raw.get(total);                                           // the thread's buffer
+        return *p ? 0 : VPS_EARG(5);
+    });
+    if (st) return st;
+    const int H = g.H, W = g.W, C = g.C;
+    const size_t stride = g.stride;
     // un-filter in place (PNG specification 9.2: None, Sub, Up, Average, Paeth; bytes of the pixel to the left = C bytes back)
     for (int y = 0; y < H; ++y) {
         uint8_t* cur = raw + (size_t)y * (stride + 1) + 1;

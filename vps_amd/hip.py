@@ -30,6 +30,7 @@ SYMBOLS = [
     'vps_unify_hist', 'vps_unify_tables', 'vps_unify_write', 'vps_image_prep', 'vps_resize_u8', 'vps_segment_stats', 'vps_segment_paint', 'vps_pair_count',
     'vps_png_info', 'vps_png_decode_bgr8', 'vps_jpeg_info', 'vps_jpeg_decode_coef', 'vps_jpeg_reconstruct',
     'vps_png_encode_bound', 'vps_png_deflate',
+    'vps_png_inflate', 'vps_png_reconstruct_ws', 'vps_png_reconstruct', 'vps_png_reconstruct_block_rows',
     'vps_unify_tables_image', 'vps_segment_stats_ch', 'vps_segment_paint_ch', 'vps_sseg_confusion',
 ]
 
@@ -90,7 +91,7 @@ def csrc_sha16():
 
 
 def load_host():
-    """the handle whose calls release the interpreter lock: the host-side functions (PNG decode, JPEG entropy decode) that decode threads run in parallel"""
+    """the handle whose calls release the interpreter lock: the host-side functions (PNG decode / inflate, JPEG entropy decode) that decode threads run in parallel"""
     load()
     return _host
 
@@ -186,12 +187,17 @@ def load():
         h.vps_png_info.restype = h.vps_png_decode_bgr8.restype = c_int
         h.vps_png_info.argtypes = [c_void_p, c_int64, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]
         h.vps_png_decode_bgr8.argtypes = [c_void_p, c_int64, c_void_p, c_int64]
+        h.vps_png_inflate.restype = c_int
+        h.vps_png_inflate.argtypes = [c_void_p, c_int64, c_void_p, c_int64]
         h.vps_jpeg_info.restype = h.vps_jpeg_decode_coef.restype = c_int
         h.vps_jpeg_info.argtypes = [c_void_p, c_int64, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
                                     c_void_p, POINTER(c_int64)]
         h.vps_jpeg_decode_coef.argtypes = [c_void_p, c_int64, c_void_p, c_int64]
     lib.vps_jpeg_reconstruct.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_int64, c_void_p,
                                          c_void_p]
+    lib.vps_png_reconstruct_ws.argtypes = [c_int, c_int, c_int, POINTER(c_int64)]
+    lib.vps_png_reconstruct.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]
+    lib.vps_png_reconstruct_block_rows.argtypes = []
     lib.vps_png_encode_bound.argtypes = [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]
     lib.vps_png_deflate.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]
     lib.vps_rpn_select.argtypes = [POINTER(c_void_p), POINTER(c_int32), POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
@@ -223,6 +229,11 @@ def load():
 
 def build_info():
     return load().vps_build_info().decode()
+
+
+def png_block_rows():
+    """rows of one band of `vps_png_reconstruct`'s wavefront (the kernel's launch constant): a group of more rows takes several bands"""
+    return int(load().vps_png_reconstruct_block_rows())
 
 
 def stream_ptr():

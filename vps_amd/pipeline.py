@@ -138,7 +138,10 @@ class ClipFeeder:
     padded fp32 tensor on the device. A baseline JPEG (the VIPER frames) is entropy-decoded by the worker the same way (`csrc/jpeg_host.cpp`): the slot then holds
     its quantised coefficients, and the consumer's upload is followed by `vps_jpeg_reconstruct` (inverse DCT, upsampling, colour
     on the device; bit-exact with libjpeg, so with cv2.imread). Files the native decoders do not take (progressive / CMYK JPEG, 16-bit
-    / palette PNG) go through `imread` and one copy into the staging buffer (`fallback_decodes`). What did NOT work (measured on the GPU box): PIL decode threads - they hold the interpreter lock
+    / palette PNG) go through `imread` and one copy into the staging buffer (`fallback_decodes`). `png='device'` (opt-in) splits a PNG the
+    same way: the worker only inflates (`vps_png_inflate`), the device un-filters and swaps to BGR (`vps_png_reconstruct`, `native_png_device`).
+    The ring's slots are sized from the FIRST file; a later PNG whose scanlines do not fit a slot (RGBA behind an RGB first file) is decoded by
+    the worker as with png='host' - the bytes are the same, only `native_png_device` stays lower. What did NOT work (measured on the GPU box): PIL decode threads - they hold the interpreter lock
     for long stretches and beside a main thread that launches ~560 kernels per frame deliver 6 frames/s; forked decode processes -
     the fork of a process that maps 30 GB of device memory stalls (1.4 frames/s). A prepared frame is kept until the consumer asks
     for a frame two positions later (frame t is frame t+1's reference), so the same tensor OBJECT serves as `img` of frame t and
@@ -149,10 +152,11 @@ class ClipFeeder:
         feeder.close()
     """
 
-    def __init__(self, files, prep, workers=4, ahead=None):
+    def __init__(self, files, prep, workers=4, ahead=None, png='host'):
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
-        self.files, self.prep = list(files), prep
+        assert png in ('host', 'device'), "png: 'host' (decode on the worker) or 'device' (inflate on the worker, un-filter on the device)"
+        self.files, self.prep, self.png = list(files), prep, png
         self.workers = int(workers)
         self.ahead = int(ahead) if ahead is not None else 2 * self.workers      # decoded frames in flight beyond the consumer
         self._pool = ThreadPoolExecutor(self.workers)
@@ -164,6 +168,7 @@ class ClipFeeder:
         self._hi = len(self.files)  # the window never runs past this frame (`set_range`: the end of a rank's shard)
         self.decodes = 0
         self.native_jpeg = 0        # frames whose entropy decode ran in the library and whose pixels the device reconstructed
+        self.native_png_device = 0  # frames a worker only inflated and whose scanlines the device un-filtered (png='device')
         self.fallback_decodes = 0   # frames that went through `imread` (files the native decoders do not take)
         self.out_of_window = 0      # requests that found their frame neither prepared nor in flight (decoded on the spot)
         self.stats = dict(wait_for_decode_s=0.0, upload_prep_s=0.0)      # where the consumer's time in __call__ went
@@ -190,7 +195,7 @@ class ClipFeeder:
     def _decode(self, path, slot):
         """worker thread: file -> staging slot; returns (H, W, tag): tag None = the slot holds the BGR frame, 'imread' = the same
         through the general decoder, a `JpegInfo` = the slot holds a JPEG's coefficients + quantisation tables (the device
-        reconstructs the frame: `jpeg_reconstruct`)"""
+        reconstructs the frame: `jpeg_reconstruct`), a `PngInfo` = the slot holds a PNG's filtered scanlines (`png_reconstruct`)"""
         lib = hip.load_host()
         size = osp.getsize(path)
         if len(self._fbuf[slot]) < size:
@@ -204,6 +209,10 @@ class ClipFeeder:
         low = str(path).lower()
         if low.endswith('.png') and lib.vps_png_info(cbuf, n, ctypes.byref(H), ctypes.byref(W), ctypes.byref(C)) == 0 \
                 and H.value * W.value * 3 <= stage.numel():
+            scan_bytes = H.value * (1 + W.value * C.value)
+            if self.png == 'device' and self.prep.device.type == 'cuda' and scan_bytes <= stage.numel():      # no CPU twin: host stand-ins decode
+                hip.check(lib.vps_png_inflate(cbuf, n, ctypes.c_void_p(stage.data_ptr()), stage.numel()), 'vps_png_inflate')
+                return H.value, W.value, PngInfo(H.value, W.value, C.value)
             hip.check(lib.vps_png_decode_bgr8(cbuf, n, ctypes.c_void_p(stage.data_ptr()), stage.numel()), 'vps_png_decode_bgr8')
             return H.value, W.value, None
         if low.endswith(('.jpg', '.jpeg')) and self.prep.device.type == 'cuda':      # the reconstruction has no CPU twin: host stand-ins use imread
@@ -235,6 +244,11 @@ class ClipFeeder:
                     ji = jpeg_info(bytearray(f.read()))
                 if ji is not None:
                     nbytes = max(nbytes, ji.coef_bytes + JPEG_QT_BYTES)
+            if self.png == 'device' and str(self.files[0]).lower().endswith('.png') and self.prep.device.type == 'cuda':
+                with open(self.files[0], 'rb') as f:                             # a PNG's slot holds its filtered scanlines (RGBA: more than the frame)
+                    pi = png_info(f.read(33))
+                if pi is not None:
+                    nbytes = max(nbytes, pi.scan_bytes)
             self._slots(nbytes)
         t_hi = min(t_hi, self._hi)
         while self._next < t_hi:
@@ -297,17 +311,21 @@ class ClipFeeder:
         self.stats['wait_for_decode_s'] += c1 - c0
         self.decodes += 1
         dev = self.prep.device
-        jpeg = isinstance(tag, JpegInfo)
+        jpeg, png = isinstance(tag, JpegInfo), isinstance(tag, PngInfo)
         self.native_jpeg += jpeg
+        self.native_png_device += png
         self.fallback_decodes += tag == 'imread'
         # a JPEG's slot holds coefficients + tables (for 4:2:0 the size of the BGR frame): uploaded as they are, the frame is rebuilt there
-        src = self._stage[slot][:tag.coef_bytes + JPEG_QT_BYTES] if jpeg else self._stage[slot][:H * W * 3].view(H, W, 3)
+        src = self._stage[slot][:tag.coef_bytes + JPEG_QT_BYTES] if jpeg else self._stage[slot][:tag.scan_bytes] if png \
+            else self._stage[slot][:H * W * 3].view(H, W, 3)
         if dev.type == 'cuda':
             d = src.to(dev, non_blocking=True)
             ev = torch.cuda.Event(); ev.record()
             self._events[slot] = ev
             if jpeg:
                 d = jpeg_reconstruct(d, tag)
+            elif png:
+                d = png_reconstruct(d, tag.H, tag.W, tag.C)
         else:
             d = src.numpy().copy()                 # host stand-in (tests): own copy, the slot goes back to the ring
         out, img_shape, pad_shape, sf = self.prep.prep(d)
@@ -384,6 +402,53 @@ def jpeg_decode(data, device='cuda'):
     hip.check(lib.vps_jpeg_decode_coef(cbuf, len(data), ctypes.c_void_p(host.data_ptr()), ji.coef_bytes), 'vps_jpeg_decode_coef')
     host[ji.coef_bytes:].copy_(torch.from_numpy(ji.qt.view(np.uint8).reshape(-1)))
     return jpeg_reconstruct(host.to(device), ji)
+
+
+class PngInfo:
+    """what `vps_png_info` reports about a file the native PNG path takes; scan_bytes = its filtered scanlines (`vps_png_inflate` output)"""
+    __slots__ = ('H', 'W', 'C', 'scan_bytes')
+
+    def __init__(self, H, W, C):
+        self.H, self.W, self.C, self.scan_bytes = H, W, C, H * (1 + W * C)
+
+
+def png_info(data):
+    """header of an 8-bit non-interlaced RGB / RGBA / grey PNG (its first 33 bytes suffice) -> PngInfo; None for any other flavour"""
+    lib = hip.load_host()
+    buf = (ctypes.c_char * len(data)).from_buffer_copy(data) if not isinstance(data, (bytearray, memoryview)) else (ctypes.c_char * len(data)).from_buffer(data)
+    H, W, C = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    if lib.vps_png_info(buf, len(data), ctypes.byref(H), ctypes.byref(W), ctypes.byref(C)) != 0:
+        return None
+    return PngInfo(H.value, W.value, C.value)
+
+
+def png_inflate(data):
+    """bytes of a PNG `png_decode` takes -> (uint8 [H * (1 + W*C)] filtered scanlines as zlib delivers them, each row led by its filter
+    byte, PngInfo) through the library's host inflate (csrc/png_host.cpp, no interpreter lock while it runs); None for any other flavour"""
+    lib = hip.load_host()
+    pi = png_info(data)
+    if pi is None:
+        return None
+    buf = (ctypes.c_char * len(data)).from_buffer_copy(data) if not isinstance(data, (bytearray, memoryview)) else (ctypes.c_char * len(data)).from_buffer(data)
+    scan = np.empty(pi.scan_bytes, dtype=np.uint8)
+    hip.check(lib.vps_png_inflate(buf, len(data), scan.ctypes.data_as(ctypes.c_void_p), scan.nbytes), 'vps_png_inflate')
+    return scan, pi
+
+
+def png_reconstruct(scan, H, W, C, ws=None):
+    """device uint8 buffer holding a PNG's filtered scanlines (`vps_png_inflate` output, at any byte offset of its storage) -> device BGR
+    uint8 [H,W,3]: the five scanline filters undone and RGB -> BGR on the current stream (csrc/png_in_ops.hip), byte for byte what
+    `png_decode` gives. `ws`: reusable device workspace of `vps_png_reconstruct_ws` bytes (the group table)."""
+    lib = hip.load()
+    need = ctypes.c_int64()
+    hip.check(lib.vps_png_reconstruct_ws(H, W, C, ctypes.byref(need)), 'vps_png_reconstruct_ws')
+    assert scan.dtype == torch.uint8 and scan.is_contiguous() and scan.numel() >= H * (1 + W * C), 'filtered scanlines of H * (1 + W*C) bytes expected'
+    if ws is None or ws.numel() < need.value:
+        ws = torch.empty(need.value, dtype=torch.uint8, device=scan.device)
+    out = torch.empty(H, W, 3, dtype=torch.uint8, device=scan.device)
+    hip.check(lib.vps_png_reconstruct(hip.ptr(scan), H, W, C, hip.ptr(out), out.numel(), hip.ptr(ws), ws.numel(), hip.stream_ptr()),
+              'vps_png_reconstruct')
+    return out
 
 
 def png_decode(data):
