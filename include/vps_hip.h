@@ -414,6 +414,39 @@ int vps_jpeg_decode_coef(const uint8_t* file, int64_t nbytes, int16_t* coef, int
 int vps_jpeg_reconstruct(const int16_t* coef, const uint16_t* qt, int H, int W, int ncomp, const int32_t* samp, const int32_t* grid,
                          uint8_t* ws, int64_t ws_bytes, uint8_t* out, void* stream);
 
+/* JPEG output (overlay images; csrc/jpeg_enc_ops.hip + csrc/jpeg_enc_host.cpp): the input path above in the other direction.
+ * Blending, RGB -> YCbCr, chroma down-sampling, the 8x8 forward DCT and quantisation run on the DEVICE and are bit-exact with
+ * libjpeg's default compressor (16-bit fixed-point colour, h2v2 box filter with the bias alternating 1, 2, slow-integer DCT, rounded
+ * division); the Huffman coding and the container are written on the HOST (no device work, no stream, no interpreter lock, no
+ * allocation, thread-safe). `subsampling` is 0 (4:4:4) or 2 (4:2:0), three components always; anything else is an argument error.
+ * Both directions share one description of a file: the coefficient layout and the block grids are those of vps_jpeg_decode_coef /
+ * vps_jpeg_info.
+ * vps_overlay_render (device; launches on `stream`, no sync, no hidden allocation): frame_bgr uint8 [H][W][3] BGR, colour_rgb uint8
+ * [H][W][3] RGB (the painted panoptic map; 0, 0, 0 = void), alpha 0..256 -> out_rgb uint8 [H][W][3] RGB, all dense DEVICE arrays.
+ * A pixel whose right or lower neighbour has another colour triple is white (the last column has no right, the last row no lower
+ * neighbour); otherwise a void pixel keeps the frame and every other one is (frame * (256 - alpha) + colour * alpha + 128) >> 8.
+ * vps_jpeg_quant_tables (HOST): qt uint16 [2][64] (luma, chroma; natural order) = the Annex K tables scaled by libjpeg's quality
+ * rule (quality 1..100), entries limited to 1..255 (baseline).
+ * vps_jpeg_encode_bound (HOST arithmetic only): grid [3][2] = (block rows, block columns) per component padded to whole MCUs and
+ * coef_bytes, the size of the coefficient array - the only buffer vps_jpeg_encode_coef needs. Either output may be NULL.
+ * vps_jpeg_encode_coef (device; launches on `stream`, no sync, no hidden allocation, no workspace): rgb uint8 [H][W][3] with
+ * row_stride >= 3 * W bytes between rows, qt as vps_jpeg_quant_tables wrote it but in DEVICE memory, coef (DEVICE, 16-byte aligned,
+ * coef_capacity >= coef_bytes) = int16 [component][block row][block column][64] in natural order, every block written: pixels are
+ * replicated to a whole block / iMCU row, the blocks that only fill the last MCU are zero but for the DC of the block before them.
+ * vps_jpeg_write_bound (HOST arithmetic only): capacity that holds the file of ANY coefficients of that size.
+ * vps_jpeg_write (HOST): coef (host memory) + qt [2][64] -> a baseline JFIF file in out: SOI, APP0, two DQT, SOF0, the four Annex K
+ * DHT, SOS, one interleaved scan, EOI; nbytes[0] = its size. A capacity that does not hold it (a smaller one than the bound is fine
+ * when the file fits) or a coefficient outside the range of 8-bit baseline data returns an argument error; no byte beyond
+ * out + capacity is ever stored. */
+int vps_overlay_render(const uint8_t* frame_bgr, const uint8_t* colour_rgb, int H, int W, int alpha, uint8_t* out_rgb, void* stream);
+int vps_jpeg_quant_tables(int quality, uint16_t* qt);
+int vps_jpeg_encode_bound(int H, int W, int subsampling, int32_t* grid, int64_t* coef_bytes);
+int vps_jpeg_encode_coef(const uint8_t* rgb, int H, int W, int64_t row_stride, int subsampling, const uint16_t* qt, int16_t* coef,
+                         int64_t coef_capacity, void* stream);
+int vps_jpeg_write_bound(int H, int W, int subsampling, int64_t* capacity);
+int vps_jpeg_write(const int16_t* coef, int H, int W, int subsampling, const uint16_t* qt, uint8_t* out, int64_t capacity,
+                   int64_t* nbytes);
+
 /* ref: models/anchor_heads/rpn_head.py:62-91 (sigmoid objectness, `scores.topk(nms_pre)`, gathers) + core/anchor/anchor_generator.py:55-72
  * (grid anchors) + core/bbox/transforms.py:34-68 (delta2bbox, means 0, clipped to the image) for ALL levels: one chip-wide scoring
  * launch + one select / sort / decode launch with one workgroup per level. cls[l] / reg[l]: NHWC maps [H_l][W_l][ld] of level l

@@ -10,7 +10,17 @@ Two map kinds at Cityscapes-VPS size, both synthetic (eight stuff bands with wav
   file sizes     the device encoder's file against PIL's (`Image.fromarray(map).save`) for both kinds
   frames/s       at two maps per frame: `DevicePngWriter` (2 workers) fed device tensors, `AsyncPngWriter` at 1, 2 and 4 workers fed
                  the host copies it needs (its 2 x 6 MB download per frame included), on the same host
-Prints one JSON line and writes it to --out, stamped with `hip.csrc_sha16()`. Needs the GPU."""
+Prints one JSON line and writes it to --out, stamped with `hip.csrc_sha16()`. Needs the GPU.
+
+`--leg overlay` measures the overlay JPEGs instead (and writes profiles/overlay_output_pipeline.json): a synthetic photographic frame
+(BGR) and the painted map of above, one overlay per frame at quality 90, 4:2:0.
+  device_ms      `vps_overlay_render` and `vps_jpeg_encode_coef`, each the median of 30, timed with events, with their algorithmic bytes
+                 over 8 TB/s (render: two inputs read, one image written; encode: the image read, the coefficients written)
+  host_ms        `vps_jpeg_write` on one thread for one frame (Huffman coding + container), and the device-to-host copy it waits for
+  file sizes     the device path's file and PIL's `save(format='JPEG', quality=90, subsampling=2)` of the same pixels (equal scans)
+  frames/s       `DeviceJpegWriter` against "download frame and colour map + NumPy blend + PIL save" on a thread pool, both with the same
+                 thread count (1, 2, 4), on the same host
+Neither side had been measured before; the report states which one wins."""
 import argparse
 import io
 import json
@@ -56,13 +66,142 @@ def pil_size(img):
     return len(b.getvalue())
 
 
+def numpy_overlay(frame_bgr, colour_rgb, alpha):
+    """the host path's blend: what `vps_overlay_render` computes, in NumPy (uint16 arithmetic)"""
+    f = frame_bgr[..., ::-1].astype(np.uint16)
+    c = colour_rgb.astype(np.uint16)
+    out = ((f * (256 - alpha) + c * alpha + 128) >> 8).astype(np.uint8)
+    void = ~colour_rgb.any(-1)
+    out[void] = frame_bgr[..., ::-1][void]
+    edge = np.zeros(void.shape, dtype=bool)
+    edge[:, :-1] |= (colour_rgb[:, :-1] != colour_rgb[:, 1:]).any(-1)
+    edge[:-1, :] |= (colour_rgb[:-1, :] != colour_rgb[1:, :]).any(-1)
+    out[edge] = 255
+    return out
+
+
+def overlay_leg(args):
+    import torch
+    from PIL import Image
+    from vps_amd import hip, synth
+    from vps_amd import postprocess as pp
+    assert torch.cuda.is_available(), 'the device encoder needs the MI355X'
+    dev = torch.device('cuda:0')
+    H, W, Q, A = args.height, args.width, 90, 128
+    colours = [painted(label_map(H, W, s), s) for s in range(4)]
+    frames = [synth.synth_frame(H, W, seed=s, shift=(2 * s, s), noise=2.0).astype(np.uint8) for s in range(4)]       # BGR
+    d_col = [torch.from_numpy(a).to(dev) for a in colours]
+    d_fr = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in frames]
+    rep = dict(mode='overlay_output', size=[H, W], frames=args.frames, quality=Q, subsampling='4:2:0', alpha=A, host_cpus=os.cpu_count(),
+               csrc_sha16=hip.csrc_sha16())
+
+    def timed(fn):
+        for _ in range(3):
+            fn(0)
+        torch.cuda.synchronize()
+        ms = []
+        for i in range(30):
+            e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
+            e0.record()
+            fn(i)
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return float(np.median(ms)), float(min(ms))
+
+    _, coef_bytes, _ = pp.jpeg_encode_bound(H, W)
+    coef = torch.empty(coef_bytes // 2, dtype=torch.int16, device=dev)
+    rgbs = [pp.render_overlay(d_fr[i], d_col[i], A) for i in range(4)]
+    med, mn = timed(lambda i: pp.render_overlay(d_fr[i % 4], d_col[i % 4], A))
+    alg = 3 * H * W * 3
+    rep['render'] = dict(device_ms_median_of_30=round(med, 4), device_ms_min=round(mn, 4), algorithmic_MB=round(alg / 1e6, 2),
+                         fraction_of_8TBps=round(alg / (med * 1e-3) / 8e12, 4))
+    med, mn = timed(lambda i: pp.jpeg_encode_coef(rgbs[i % 4], Q, '4:2:0', coef))
+    alg = H * W * 3 + coef_bytes
+    rep['encode_coef'] = dict(device_ms_median_of_30=round(med, 4), device_ms_min=round(mn, 4), algorithmic_MB=round(alg / 1e6, 2),
+                              fraction_of_8TBps=round(alg / (med * 1e-3) / 8e12, 4), coefficient_MB=round(coef_bytes / 1e6, 2))
+    # host side of one frame, one thread
+    pinned = torch.empty(coef_bytes // 2, dtype=torch.int16).pin_memory()
+    pp.jpeg_encode_coef(rgbs[1], Q, '4:2:0', coef)
+    torch.cuda.synchronize()
+    cp, wr = [], []
+    buf = np.empty(pp.jpeg_encode_bound(H, W)[2], dtype=np.uint8)
+    for _ in range(10):
+        t0 = time.perf_counter()
+        pinned.copy_(coef, non_blocking=True)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        data = pp.jpeg_write(pinned, H, W, Q, '4:2:0', buf)
+        t2 = time.perf_counter()
+        cp.append(1e3 * (t1 - t0)); wr.append(1e3 * (t2 - t1))
+    b = io.BytesIO()
+    host_rgb = rgbs[1].cpu().numpy()
+    Image.fromarray(host_rgb).save(b, format='JPEG', quality=Q, subsampling=2, optimize=False)
+    ref = b.getvalue()
+    assert data[data.index(b'\xff\xda'):] == ref[ref.index(b'\xff\xda'):], 'the scan differs from PIL\'s'
+    assert np.array_equal(host_rgb, numpy_overlay(frames[1], colours[1], A)), 'the host blend is not the device blend'
+    rep['host_one_frame'] = dict(copy_ms_median_of_10=round(float(np.median(cp)), 3), jpeg_write_ms_median_of_10=round(float(np.median(wr)), 3))
+    rep['file'] = dict(device_file_bytes=len(data), pil_file_bytes=len(ref), scan_equal_to_pil=True, raw_over_file=round(H * W * 3 / len(data), 1))
+
+    def run_device(workers):
+        w = pp.DeviceJpegWriter(dev, workers=workers, slots=8, quality=Q)
+        with tempfile.TemporaryDirectory() as tmp:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for f in range(args.frames):
+                w.submit(pp.render_overlay(d_fr[f % 4], d_col[f % 4], A), os.path.join(tmp, '%04d.jpg' % f))
+            t_submit = time.perf_counter() - t0
+            w.close()
+            dt = time.perf_counter() - t0
+        assert w.device_encoded == args.frames
+        return dict(frames_per_s=round(args.frames / dt, 1), submit_s=round(t_submit, 4), total_s=round(dt, 4), MB_written=round(w.bytes_written / 1e6, 2))
+
+    def run_host(workers):
+        from concurrent.futures import ThreadPoolExecutor
+
+        def job(fr, col, name):
+            Image.fromarray(numpy_overlay(fr, col, A)).save(name, format='JPEG', quality=Q, subsampling=2, optimize=False)
+            return os.path.getsize(name)
+        with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(workers) as pool:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            futs = []
+            for f in range(args.frames):
+                fr, col = d_fr[f % 4].cpu().numpy(), d_col[f % 4].cpu().numpy()      # the download the host path needs
+                futs.append(pool.submit(job, fr, col, os.path.join(tmp, '%04d.jpg' % f)))
+            t_submit = time.perf_counter() - t0
+            nbytes = sum(x.result() for x in futs)
+            dt = time.perf_counter() - t0
+        return dict(frames_per_s=round(args.frames / dt, 1), submit_s=round(t_submit, 4), total_s=round(dt, 4), MB_written=round(nbytes / 1e6, 2))
+
+    run_device(2)                                                    # warm-up: ring slots, pinned staging, copy streams
+    run_host(2)
+    rep['device_writer'] = {str(n): run_device(n) for n in (1, 2, 4)}
+    rep['host_numpy_pil'] = {str(n): run_host(n) for n in (1, 2, 4)}
+    rep['verdict'] = {str(n): ('device path %s: %.1f vs %.1f frames/s' % ('wins' if rep['device_writer'][str(n)]['frames_per_s'] > rep['host_numpy_pil'][str(n)]['frames_per_s'] else 'LOSES',
+                                                                        rep['device_writer'][str(n)]['frames_per_s'], rep['host_numpy_pil'][str(n)]['frames_per_s'])) for n in (1, 2, 4)}
+    rep['not_measured'] = 'a clip of the detector with --overlay against the same clip without it'
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--leg', default='png', choices=['png', 'overlay'])
     ap.add_argument('--frames', type=int, default=30)
     ap.add_argument('--height', type=int, default=1024)
     ap.add_argument('--width', type=int, default=2048)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'png_output_pipeline.json'))
+    ap.add_argument('--out', default=None, help='default: profiles/png_output_pipeline.json, or profiles/overlay_output_pipeline.json for --leg overlay')
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'png_output_pipeline.json' if args.leg == 'png' else 'overlay_output_pipeline.json')
+    if args.leg == 'overlay':
+        line = json.dumps(overlay_leg(args))
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, 'w') as f:
+                f.write(line + '\n')
+        return
     import torch
     from vps_amd import hip
     from vps_amd import postprocess as pp

@@ -51,6 +51,10 @@ def parse_args(argv=None):
     ap.add_argument('--strict', action='store_true', help='load_checkpoint(strict=True): missing / unexpected keys are fatal')
     ap.add_argument('--png-workers', type=int, default=6)
     ap.add_argument('--device-png', action='store_true', help='encode the result PNGs on the device (postprocess.DevicePngWriter) instead of PIL threads')
+    ap.add_argument('--overlay', default=None, metavar='DIR', help='write DIR/<name>.jpg for every frame: the panoptic result blended over the frame (off by default; '
+                    'keeps every decoded frame on the device until the maps are unified, 6 MB per frame at 1024x2048)')
+    ap.add_argument('--overlay-quality', type=int, default=90)
+    ap.add_argument('--overlay-alpha', type=int, default=128, help='weight of the colour map, 0..256')
     ap.add_argument('--dry-run', action='store_true')
     ap.add_argument('--dry-size', default='128x256'); ap.add_argument('--dry-videos', type=int, default=1); ap.add_argument('--dry-frames', type=int, default=16)
     ap.add_argument('--check-only', action='store_true')
@@ -153,8 +157,8 @@ def run(args, tmp):
     model.ensure_packed(dev)
     prep = DeviceImagePrep(**cfg.img_norm_cfg, size_divisor=32, img_scale=(2048, 1024), device=dev)
     files = [os.path.join(img_prefix, x['file_name']) for x in info]
-    feeder = ClipFeeder(files, prep, workers=args.png_workers).start()
-    res = dict(all_names=[], all_ssegs=[], all_panos=[], all_pano_cls_inds=[], all_pano_obj_ids=[])
+    feeder = ClipFeeder(files, prep, workers=args.png_workers, keep_frames=bool(args.overlay)).start()
+    res = dict(all_names=[], all_ssegs=[], all_panos=[], all_pano_cls_inds=[], all_pano_obj_ids=[], all_frames=[])
     t0 = time.perf_counter()
     with torch.no_grad():
         for idx, im in enumerate(info):
@@ -169,6 +173,8 @@ def run(args, tmp):
             res['all_pano_cls_inds'].append(result[2]['panoptic_cls_inds'].cpu().numpy())
             res['all_pano_obj_ids'].append(result[2]['panoptic_det_obj_ids'].cpu().numpy())
             res['all_names'].append(os.path.basename(files[idx]))
+            if args.overlay:
+                res['all_frames'].append(feeder.frame(idx))       # the decoded BGR frame the feeder holds anyway
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     feeder.close()
@@ -193,6 +199,13 @@ def run(args, tmp):
     pans, pj = inference_panoptic_video(pred_pans_2ch, output_dir, categories, names, n_video=args.n_video, color_generator=gen, device=dev, **kw)
     if args.device_png:
         kw['writer'].close()
+    if args.overlay:
+        from run_vps_synthetic import ColorGenerator
+        from vps_amd.postprocess import write_overlays
+        order = sorted(range(len(res['all_names'])), key=lambda i: res['all_names'][i])                # the order of pred_pans_2ch
+        ov = write_overlays(pred_pans_2ch, [res['all_frames'][i] for i in order], [res['all_names'][i] for i in order], args.overlay,
+                            ColorGenerator({c['id']: c for c in categories}), span, device=dev, quality=args.overlay_quality, alpha=args.overlay_alpha)
+        report['overlay'] = dict(dir=args.overlay, files=len(ov), quality=args.overlay_quality, alpha=args.overlay_alpha)
     report['run'] = dict(frames=len(info), seconds=round(dt, 3), frames_per_s=round(len(info) / dt, 2), decodes=feeder.decodes, output_dir=output_dir,
                          png_files=len(os.listdir(os.path.join(output_dir, 'pan_pred'))))
     truth_dir, gt_json = args.truth_dir, args.pan_gt_json

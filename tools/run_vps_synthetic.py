@@ -71,7 +71,7 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False):
         nhwc.DEFAULT_PREC = old
     prep = DeviceImagePrep(**cfg.img_norm_cfg, size_divisor=32, img_scale=(max(H, W), min(H, W)), device=dev)
     feed = PairFeeder(prep)
-    res = dict(all_names=[], all_ssegs=[], all_panos=[], all_pano_cls_inds=[], all_pano_obj_ids=[])
+    res = dict(all_names=[], all_ssegs=[], all_panos=[], all_pano_cls_inds=[], all_pano_obj_ids=[], all_frames=[])
     decoded = [[uint8_frame(H, W, seed=v, shift=(2 * f, f)) for f in range(nframes)] for v in range(videos)]   # "cv2.imread" results (BGR uint8)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -89,14 +89,16 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False):
             res['all_pano_cls_inds'].append(result[2]['panoptic_cls_inds'].cpu().numpy())
             res['all_pano_obj_ids'].append(result[2]['panoptic_det_obj_ids'].cpu().numpy())
             res['all_names'].append(name)
+            res['all_frames'].append(decoded[v][f])                                # the decoded frame itself: what --overlay draws on
     torch.cuda.synchronize()
     return res, time.perf_counter() - t0
 
 
-def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_png=False):
+def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_png=False, overlay=None):
     """test_vpq.py:178-198 with the device-side unifier / converter / asynchronous writer (`device_png`: the PNGs are filtered and
-    deflated on the device too, postprocess.DevicePngWriter)"""
-    from vps_amd.postprocess import DevicePngWriter, PanopticUnifier, inference_panoptic_video
+    deflated on the device too, postprocess.DevicePngWriter). `overlay` = (directory, quality, alpha): an overlay JPEG of EVERY frame,
+    blended and transformed on the device (postprocess.write_overlays)"""
+    from vps_amd.postprocess import DevicePngWriter, PanopticUnifier, inference_panoptic_video, write_overlays
     unifier = PanopticUnifier(dev, 19, 9)
     two = unifier.get_unified_pan_result(res['all_ssegs'], res['all_panos'], res['all_pano_cls_inds'], obj_ids=res['all_pano_obj_ids'],
                                          stuff_area_limit=2048, names=res['all_names'])
@@ -109,6 +111,13 @@ def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_pn
                                         labeled_fid=labeled_fid, lambda_=lambda_, nframes_per_video=nper, writer=writer)
     if writer is not None:
         writer.close()
+    if overlay:
+        # (synth_frame crops the late, far-shifted frames of a clip at the edge of its noise field while img_meta keeps the nominal
+        # size: such a frame is padded back to the size of its map with its edge pixels)
+        frames = {n: np.pad(f, ((0, two[n].shape[0] - f.shape[0]), (0, two[n].shape[1] - f.shape[1]), (0, 0)), mode='edge')
+                  for n, f in zip(res['all_names'], res['all_frames'])}
+        write_overlays(pred_pans_2ch, [frames[k] for k in keys], keys, overlay[0], ColorGenerator(cats), len(keys) // max(videos, 1), device=dev,
+                       quality=overlay[1], alpha=overlay[2])
     return names, pans, pj
 
 
@@ -141,13 +150,17 @@ def main():
     ap.add_argument('--separated', action='store_true', help='box classification layer of tests/golden/separated_fc_cls.npz (few, well-separated detections)')
     ap.add_argument('--out', default=os.path.join(ROOT, 'gpurun_out', 'vps_synth'))
     ap.add_argument('--device-png', action='store_true', help='encode the result PNGs on the device (postprocess.DevicePngWriter) instead of PIL threads')
+    ap.add_argument('--overlay', default=None, metavar='DIR', help='write DIR/<name>.jpg for every frame: the panoptic result blended over the frame (off by default)')
+    ap.add_argument('--overlay-quality', type=int, default=90)
+    ap.add_argument('--overlay-alpha', type=int, default=128, help='weight of the colour map, 0..256')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     labeled_fid, lambda_ = 20, 5
+    overlay = (args.overlay, args.overlay_quality, args.overlay_alpha) if args.overlay else None
     nper = len(range(labeled_fid // lambda_, args.frames, lambda_))
     res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated)
     t0 = time.perf_counter()
-    names, pans, pj = postprocess(res, os.path.join(args.out, 'pred'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png)
+    names, pans, pj = postprocess(res, os.path.join(args.out, 'pred'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png, overlay)
     dpost = time.perf_counter() - t0
     pred = (pans, pj)
     gt = pred
@@ -160,7 +173,7 @@ def main():
     deval = time.perf_counter() - t0
     files = sorted(os.listdir(os.path.join(args.out, 'pred', 'pan_pred')))
     report = dict(videos=args.videos, frames_per_video=args.frames, size=[args.height, args.width], prec=args.prec, gt=args.gt_prec or 'self', weights='synthetic seed 0' + (' + separated fc_cls' if args.separated else ''),
-                  labelled_frames=len(names), png_files=len(files), vpq=round(score['vpq'], 4),
+                  labelled_frames=len(names), png_files=len(files), overlay_files=len(os.listdir(args.overlay)) if args.overlay else 0, vpq=round(score['vpq'], 4),
                   pq_per_window={str(k): round(100 * score[k]['pq'], 4) for k in (1, 2, 3, 4)},
                   seconds=dict(model=round(dt, 3), postprocess_and_png=round(dpost, 3), eval=round(deval, 3)),
                   frames_per_s_upload_prep_model_sequential=round(args.videos * args.frames / dt, 2))

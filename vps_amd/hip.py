@@ -32,6 +32,7 @@ SYMBOLS = [
     'vps_png_encode_bound', 'vps_png_deflate',
     'vps_png_inflate', 'vps_png_reconstruct_ws', 'vps_png_reconstruct', 'vps_png_reconstruct_block_rows',
     'vps_unify_tables_image', 'vps_segment_stats_ch', 'vps_segment_paint_ch', 'vps_sseg_confusion',
+    'vps_overlay_render', 'vps_jpeg_quant_tables', 'vps_jpeg_encode_bound', 'vps_jpeg_encode_coef', 'vps_jpeg_write_bound', 'vps_jpeg_write',
 ]
 
 
@@ -91,7 +92,7 @@ def csrc_sha16():
 
 
 def load_host():
-    """the handle whose calls release the interpreter lock: the host-side functions (PNG decode / inflate, JPEG entropy decode) that decode threads run in parallel"""
+    """the handle whose calls release the interpreter lock: the host-side functions (PNG decode / inflate, JPEG entropy decode and encode) that decode / writer threads run in parallel"""
     load()
     return _host
 
@@ -193,8 +194,15 @@ def load():
         h.vps_jpeg_info.argtypes = [c_void_p, c_int64, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
                                     c_void_p, POINTER(c_int64)]
         h.vps_jpeg_decode_coef.argtypes = [c_void_p, c_int64, c_void_p, c_int64]
+        h.vps_jpeg_quant_tables.restype = h.vps_jpeg_encode_bound.restype = h.vps_jpeg_write_bound.restype = h.vps_jpeg_write.restype = c_int
+        h.vps_jpeg_quant_tables.argtypes = [c_int, c_void_p]
+        h.vps_jpeg_encode_bound.argtypes = [c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int64)]
+        h.vps_jpeg_write_bound.argtypes = [c_int, c_int, c_int, POINTER(c_int64)]
+        h.vps_jpeg_write.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, POINTER(c_int64)]
     lib.vps_jpeg_reconstruct.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_int64, c_void_p,
                                          c_void_p]
+    lib.vps_overlay_render.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+    lib.vps_jpeg_encode_coef.argtypes = [c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p]
     lib.vps_png_reconstruct_ws.argtypes = [c_int, c_int, c_int, POINTER(c_int64)]
     lib.vps_png_reconstruct.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]
     lib.vps_png_reconstruct_block_rows.argtypes = []

@@ -152,7 +152,7 @@ class ClipFeeder:
         feeder.close()
     """
 
-    def __init__(self, files, prep, workers=4, ahead=None, png='host'):
+    def __init__(self, files, prep, workers=4, ahead=None, png='host', keep_frames=False):
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         assert png in ('host', 'device'), "png: 'host' (decode on the worker) or 'device' (inflate on the worker, un-filter on the device)"
@@ -163,6 +163,8 @@ class ClipFeeder:
         self._pending = {}          # t -> (future, staging slot)
         self._ready = {}            # t -> prepared device tensor [1,3,Hp,Wp]
         self._meta = {}             # t -> shapes of the prepared frame (img_meta entries)
+        self.keep_frames = bool(keep_frames)
+        self._frames = {}           # t -> decoded BGR uint8 frame (keep_frames: what an overlay is drawn on), dropped with _ready
         self._done = set()          # frames delivered so far: the window does not decode them a second time (consumers keep what they got)
         self._next = 0              # first index not yet submitted
         self._hi = len(self.files)  # the window never runs past this frame (`set_range`: the end of a rank's shard)
@@ -330,6 +332,8 @@ class ClipFeeder:
             d = src.numpy().copy()                 # host stand-in (tests): own copy, the slot goes back to the ring
         out, img_shape, pad_shape, sf = self.prep.prep(d)
         out = out.unsqueeze(0)
+        if self.keep_frames:
+            self._frames[t] = getattr(self.prep, '_keep', d)      # the uint8 frame the normalisation read: after Resize, the size of the result maps
         self._meta[t] = dict(img_shape=tuple(img_shape), pad_shape=tuple(pad_shape), scale_factor=sf, ori_shape=(H, W, 3), flip=False)
         self.stats['upload_prep_s'] += time.perf_counter() - c1
         self._free.append(slot)                    # to the BACK of the ring: it is reused after every other free slot
@@ -338,7 +342,13 @@ class ClipFeeder:
         self._ready[t] = out
         for old in [k for k in self._ready if k < t - 1]:      # frame t-1 stays: it is frame t's reference
             del self._ready[old]
+            self._frames.pop(old, None)
         return out
+
+    def frame(self, t):
+        """the decoded BGR uint8 [H,W,3] frame t at the size the detector saw it (after `Resize`, before Normalize / Pad; a device tensor
+        on a device feeder); only with `keep_frames=True` and only while frame t is in the window (t or t-1 of the last request)"""
+        return self._frames[t]
 
     def close(self):
         for fut, slot in self._pending.values():

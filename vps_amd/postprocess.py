@@ -373,6 +373,237 @@ class DevicePngWriter:
         return names
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# Overlay images: the panoptic result blended over the input frame, written as a baseline JPEG. Blend, colour conversion, chroma
+# down-sampling, forward DCT and quantisation on the device (csrc/jpeg_enc_ops.hip), Huffman coding and the container on the host
+# without the interpreter lock (csrc/jpeg_enc_host.cpp): the JPEG input path of pipeline.py in the other direction. The files are the
+# ones libjpeg's default compressor (PIL's `save(format='JPEG', quality=q, subsampling=s)`) writes for the same pixels, scan byte for
+# scan byte.
+# ------------------------------------------------------------------------------------------------------------------
+JPEG_SUBSAMPLING = {'4:2:0': 2, '4:4:4': 0, 2: 2, 0: 0}                         # the numbers are PIL's `subsampling=` values
+_jpeg_qt_cache = {}
+
+
+def _subsampling(s):
+    if s not in JPEG_SUBSAMPLING:
+        raise ValueError("subsampling is '4:2:0' or '4:4:4', got %r" % (s,))
+    return JPEG_SUBSAMPLING[s]
+
+
+def jpeg_quant_tables(quality):
+    """uint16 [2][64] (luma, chroma; natural order): the Annex K tables scaled by libjpeg's quality rule, baseline forced"""
+    import ctypes
+    qt = np.zeros((2, 64), dtype=np.uint16)
+    hip.check(hip.load_host().vps_jpeg_quant_tables(int(quality), qt.ctypes.data_as(ctypes.c_void_p)), 'vps_jpeg_quant_tables')
+    return qt
+
+
+def _jpeg_qt(quality, device):
+    """(host tables, the same on `device`), made once per quality and device"""
+    key = (int(quality), str(device))
+    if key not in _jpeg_qt_cache:
+        qt = jpeg_quant_tables(quality)
+        _jpeg_qt_cache[key] = (qt, torch.from_numpy(qt.view(np.int16)).to(device))
+    return _jpeg_qt_cache[key]
+
+
+def jpeg_encode_bound(H, W, subsampling='4:2:0'):
+    """(block grid [(rows, columns)] x 3, bytes of the coefficient array, worst-case bytes of the file) of one image size"""
+    import ctypes
+    sub = _subsampling(subsampling)
+    host = hip.load_host()
+    grid, nb, cap = (ctypes.c_int32 * 6)(), ctypes.c_int64(0), ctypes.c_int64(0)
+    hip.check(host.vps_jpeg_encode_bound(H, W, sub, grid, ctypes.byref(nb)), 'vps_jpeg_encode_bound')
+    hip.check(host.vps_jpeg_write_bound(H, W, sub, ctypes.byref(cap)), 'vps_jpeg_write_bound')
+    return [(grid[2 * c], grid[2 * c + 1]) for c in range(3)], nb.value, cap.value
+
+
+def _device_u8(a, device):
+    t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+    assert t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3, 'uint8 [H,W,3], got %s %s' % (t.dtype, tuple(t.shape))
+    return t.to(device)
+
+
+def render_overlay(frame, colour, alpha=128):
+    """`frame` BGR uint8 [H,W,3] (as the clip feeder decodes it), `colour` RGB uint8 [H,W,3] (as `TrackConverter.convert_device` paints
+    it; 0,0,0 = void), alpha 0..256 -> device RGB uint8 [H,W,3] on the current stream, no sync (`vps_overlay_render`): void pixels keep
+    the frame, the others are (frame * (256 - alpha) + colour * alpha + 128) >> 8, and a pixel whose right or lower neighbour has another
+    colour is white. Host arrays are uploaded to the other argument's device (both on the host: 'cuda')."""
+    dev = next((t.device for t in (colour, frame) if torch.is_tensor(t) and t.is_cuda), torch.device('cuda'))
+    frame, colour = _device_u8(frame, dev).contiguous(), _device_u8(colour, dev).contiguous()
+    assert frame.shape == colour.shape, (tuple(frame.shape), tuple(colour.shape))
+    if not 0 <= int(alpha) <= 256:
+        raise ValueError('alpha is 0..256, got %r' % (alpha,))
+    out = torch.empty_like(colour)
+    hip.check(hip.load().vps_overlay_render(hip.ptr(frame), hip.ptr(colour), int(frame.shape[0]), int(frame.shape[1]), int(alpha), hip.ptr(out),
+                                            hip.stream_ptr()), 'vps_overlay_render')
+    return out
+
+
+def jpeg_encode_coef(rgb, quality=90, subsampling='4:2:0', out=None):
+    """device RGB uint8 [H,W,3] (rows may be strided) -> device int16 quantised coefficients [component][block row][block column][64] in
+    natural order - the array `vps_jpeg_decode_coef` reads from the file libjpeg writes for these pixels - on the current stream, no sync
+    (`vps_jpeg_encode_coef`). `out`: caller-owned int16 buffer of at least `jpeg_encode_bound(..)[1] / 2` elements."""
+    t, H, W, C, stride = _png_view(rgb)
+    assert C == 3, 'jpeg_encode_coef takes an RGB image [H,W,3]'
+    sub = _subsampling(subsampling)
+    _, nb, _ = jpeg_encode_bound(H, W, sub)
+    if out is None:
+        out = torch.empty(nb // 2, dtype=torch.int16, device=t.device)
+    assert out.dtype == torch.int16 and out.is_cuda and out.numel() * 2 >= nb
+    _, qt_dev = _jpeg_qt(quality, t.device)
+    hip.check(hip.load().vps_jpeg_encode_coef(hip.ptr(t), H, W, stride, sub, hip.ptr(qt_dev), hip.ptr(out), out.numel() * 2, hip.stream_ptr()),
+              'vps_jpeg_encode_coef')
+    return out[:nb // 2]
+
+
+def jpeg_write(coef, H, W, quality=90, subsampling='4:2:0', out=None):
+    """HOST int16 coefficients (numpy, or a CPU tensor such as pinned staging) -> the bytes of the baseline JFIF file (`vps_jpeg_write`,
+    no interpreter lock while it runs). `out`: reusable uint8 numpy buffer; it is grown to the worst case when the file does not fit."""
+    import ctypes
+    sub = _subsampling(subsampling)
+    qt = jpeg_quant_tables(quality)
+    _, nb, cap = jpeg_encode_bound(H, W, sub)
+    if torch.is_tensor(coef):
+        assert not coef.is_cuda and coef.dtype == torch.int16 and coef.is_contiguous() and coef.numel() * 2 >= nb
+        cptr = ctypes.c_void_p(coef.data_ptr())
+    else:
+        coef = np.ascontiguousarray(coef, dtype=np.int16)
+        assert coef.size * 2 >= nb
+        cptr = coef.ctypes.data_as(ctypes.c_void_p)
+    if out is None:
+        out = np.empty(cap, dtype=np.uint8)
+    n = ctypes.c_int64(0)
+    hip.check(hip.load_host().vps_jpeg_write(cptr, H, W, sub, qt.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p), out.size,
+                                             ctypes.byref(n)), 'vps_jpeg_write')
+    return out[:n.value].tobytes()
+
+
+def jpeg_encode(rgb, quality=90, subsampling='4:2:0'):
+    """device RGB uint8 [H,W,3] -> bytes of a baseline JPEG, the file PIL's `save(format='JPEG', quality=quality, subsampling=subsampling)`
+    writes from the SOS marker on. Synchronises (one download of the coefficients); `DeviceJpegWriter` is the asynchronous form."""
+    t, H, W, _, _ = _png_view(rgb)
+    coef = jpeg_encode_coef(t, quality, subsampling)
+    return jpeg_write(coef.cpu().numpy(), H, W, quality, subsampling)
+
+
+class _JpegSlot:
+    def __init__(self, device):
+        self.device = device
+        self.coef = self.host = self.image = None
+        self.event = torch.cuda.Event()
+
+    def fit(self, nelem):
+        if self.coef is None or self.coef.numel() < nelem:
+            self.coef = torch.empty(nelem, dtype=torch.int16, device=self.device)
+            self.host = torch.empty(nelem, dtype=torch.int16).pin_memory()
+
+
+class DeviceJpegWriter:
+    """`DevicePngWriter`'s shape for JPEG files: `submit(device RGB uint8 [H,W,3], name)` enqueues `jpeg_encode_coef` on the CURRENT stream
+    into one of `slots` ring slots (coefficients on the device + pinned staging of the same size, grown if a larger image comes), records
+    an event and returns - it never synchronises the caller's stream and blocks only while every slot is busy. A worker thread waits for
+    the event, downloads the coefficients on its own copy stream, runs `vps_jpeg_write` (no interpreter lock) into a buffer it keeps, and
+    writes the file. Host arrays are uploaded first: there is no host encoder here. Counters: `submitted`, `device_encoded`,
+    `bytes_written`. `close()` joins and re-raises a worker's exception."""
+    accepts_device = True
+
+    def __init__(self, device='cuda', workers=2, slots=4, quality=90, subsampling='4:2:0'):
+        import queue
+        import threading
+        from concurrent.futures import ThreadPoolExecutor
+        self.device = torch.device(device)
+        self.quality, self.subsampling = int(quality), _subsampling(subsampling)
+        jpeg_quant_tables(self.quality)                  # a bad quality raises here, not in a worker
+        self.pool = ThreadPoolExecutor(max_workers=workers)
+        self.futures = []
+        self.free = queue.Queue()
+        for _ in range(slots):
+            self.free.put(_JpegSlot(self.device))
+        self.local = threading.local()
+        self.lock = threading.Lock()
+        self.submitted = 0           # images handed to submit()
+        self.device_encoded = 0      # files written from device coefficients
+        self.bytes_written = 0
+
+    def _finish(self, slot, name, H, W, nelem):
+        try:
+            slot.event.synchronize()                     # the worker waits, not the caller
+            if not hasattr(self.local, 'stream'):
+                self.local.stream = torch.cuda.Stream(self.device)
+                self.local.out = None
+            with torch.cuda.stream(self.local.stream):
+                slot.host[:nelem].copy_(slot.coef[:nelem], non_blocking=True)
+                self.local.stream.synchronize()
+            cap = jpeg_encode_bound(H, W, self.subsampling)[2]
+            if self.local.out is None or self.local.out.size < cap:
+                self.local.out = np.empty(cap, dtype=np.uint8)    # pages of the worst case that no file reaches are never touched
+            data = jpeg_write(slot.host, H, W, self.quality, self.subsampling, self.local.out)
+        finally:
+            slot.image = None
+            self.free.put(slot)
+        os.makedirs(os.path.dirname(name) or '.', exist_ok=True)
+        with open(name, 'wb') as f:
+            f.write(data)
+        with self.lock:
+            self.device_encoded += 1
+            self.bytes_written += len(data)
+        return name
+
+    def submit(self, image, name):
+        if not (torch.is_tensor(image) and image.is_cuda):
+            image = _device_u8(image, self.device)
+        t, H, W, C, _ = _png_view(image)
+        assert C == 3, 'a JPEG overlay is an RGB image [H,W,3]'
+        nelem = jpeg_encode_bound(H, W, self.subsampling)[1] // 2
+        slot = self.free.get()                           # blocks only when every slot is in flight
+        try:
+            slot.fit(nelem)
+            slot.image = t                               # alive until the worker is done with it
+            jpeg_encode_coef(t, self.quality, self.subsampling, slot.coef)
+            slot.event.record()
+        except BaseException:
+            slot.image = None
+            self.free.put(slot)
+            raise
+        self.submitted += 1
+        self.futures.append(self.pool.submit(self._finish, slot, name, H, W, nelem))
+
+    def close(self):
+        futures, self.futures = self.futures, []
+        try:
+            names = [f.result() for f in futures]        # re-raises a worker's exception
+        finally:
+            self.pool.shutdown()
+        return names
+
+
+def overlay_name(save_folder, name):
+    """output file of the overlay of an input image name: DIR/<name without its extension>.jpg"""
+    return os.path.join(save_folder, os.path.splitext(os.path.basename(name))[0] + '.jpg')
+
+
+def write_overlays(pred_pans_2ch, frames, names, out_dir, color_generator, nframes_per_video, device='cuda', alpha=128, quality=90,
+                   writer=None):
+    """an overlay JPEG of EVERY frame: `pred_pans_2ch` (the unified 3-channel maps, host or device) are painted per video by
+    `TrackConverter.convert_device` (a track keeps its colour through its video), blended over `frames` (BGR uint8 [H,W,3], host or
+    device, same order) by `render_overlay` and written as `out_dir/<name>.jpg` through a `DeviceJpegWriter` (the caller's, or one made
+    and closed here). `color_generator`: its own instance - the colours of pred.json are not touched. Returns the file names."""
+    assert len(pred_pans_2ch) == len(frames) == len(names)
+    own = writer is None
+    writer = DeviceJpegWriter(device, quality=quality) if own else writer
+    conv = TrackConverter(device)
+    out = []
+    for v0 in range(0, len(pred_pans_2ch), nframes_per_video):
+        _, pans_dev, _ = conv.convert_device(pred_pans_2ch[v0:v0 + nframes_per_video], color_generator)
+        for j, pan in enumerate(pans_dev):
+            out.append(overlay_name(out_dir, names[v0 + j]))
+            writer.submit(render_overlay(frames[v0 + j], pan, alpha), out[-1])
+    if own:
+        writer.close()
+    return out
+
+
 def png_name(save_folder, name):
     """cityscapes_vps.py:73 (save_image): output file name of an input image name"""
     return os.path.join(save_folder, name.replace('_leftImg8bit', '').replace('_newImg8bit', '').replace('jpg', 'png').replace('jpeg', 'png'))
