@@ -575,6 +575,19 @@ int vps_png_encode_bound(int H, int W, int channels, int64_t* out_capacity, int6
 int vps_png_deflate(const uint8_t* img, int H, int W, int channels, int64_t row_stride, uint8_t* out, int64_t out_capacity,
                     int64_t* out_nbytes, void* ws, int64_t ws_bytes, void* stream);
 
+/* Optical-flow output (csrc/flow_vis_ops.hip; vps_amd/flowvis.py): the colour coding of the reference's flow_utils.py (vis_flow) on the
+ * device. Both launch on `stream`, no sync, no hidden allocation. flow: DEVICE fp32 NHWC map of H x W pixels, pixel p at
+ * flow[p * ld + coff] (u) and [p * ld + coff + 1] (v); coff + 2 <= ld. A pixel with u > 1e9 or v > 1e9 (unknown flow) counts as (0, 0).
+ *   vps_flow_max_radius  out (DEVICE double [1], 8-byte aligned) = max sqrt(u*u + v*v) over the frame in fp64; the call itself sets it
+ *                        to 0 on the stream first
+ *   vps_flow_colour      rgb (DEVICE uint8 [H][W][3], dense, 4-byte aligned) = vis_flow(flow.astype(float64)) with the normaliser
+ *                        max_rad[0] (DEVICE double [1]): u, v /= max_rad + DBL_EPSILON; hue from atan2(-v, -u) over the 55-entry colour
+ *                        wheel; radius <= 1: col = 1 - radius * (1 - col), else col * 0.75; floor(255 * col). fp64, no contraction.
+ *                        The frame's own vps_flow_max_radius result is the reference's behaviour; a fixed value keeps a clip's colours
+ *                        steady. NaN flow is not handled. */
+int vps_flow_max_radius(const float* flow, int ld, int coff, int H, int W, double* out, void* stream);
+int vps_flow_colour(const float* flow, int ld, int coff, int H, int W, const double* max_rad, uint8_t* rgb, void* stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Input preparation: Normalize -> Pad(size_divisor) -> ImageToTensor of the test pipeline in one pass.
  * Replaces mmdet/datasets/pipelines/transforms.py:258-269, :310-318 and formating.py:52-67 (mmcv 0.2.14 imnormalize,

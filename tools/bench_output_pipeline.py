@@ -20,7 +20,15 @@ Prints one JSON line and writes it to --out, stamped with `hip.csrc_sha16()`. Ne
   file sizes     the device path's file and PIL's `save(format='JPEG', quality=90, subsampling=2)` of the same pixels (equal scans)
   frames/s       `DeviceJpegWriter` against "download frame and colour map + NumPy blend + PIL save" on a thread pool, both with the same
                  thread count (1, 2, 4), on the same host
-Neither side had been measured before; the report states which one wins."""
+Neither side had been measured before; the report states which one wins.
+
+`--leg flow` measures the optical-flow output (and writes profiles/flow_output_pipeline.json): a synthetic flow field (smooth motion
+plus noise) in FlowNet2's layout (NHWC, pixel stride 4), one file per frame.
+  device_ms      `vps_flow_max_radius` and `vps_flow_colour`, each the median of 30, timed with events, with their algorithmic bytes over
+                 8 TB/s (the whole strided map read - the 16-byte pixels share cache lines with their padding; colour: + the image written)
+  frames/s       `FlowWriter` at 1, 2 and 4 workers for 'jpg' and 'flo' against the host way on as many threads: download the two flow
+                 channels (16.8 MB), the NumPy restatement of the colour coding (tests/flow_vis_restate.py) + PIL save for 'jpg', header
+                 + `tofile` for 'flo'; each figure is the median of --repeats windows of --frames frames, with the slowest and fastest"""
 import argparse
 import io
 import json
@@ -184,18 +192,127 @@ def overlay_leg(args):
     return rep
 
 
+def flow_field(H, W, seed):
+    """float32 [H,W,2]: a pan plus a zoom about a moving centre plus noise - a few pixels of motion, like consecutive video frames"""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+    cx, cy = W * (0.4 + 0.05 * seed), H * 0.5
+    u = 2.0 + 0.004 * (xx - cx) + 1.5 * np.sin(yy / (H / 5.0) + seed) + rng.normal(0, 0.2, (H, W))
+    v = -0.5 + 0.004 * (yy - cy) + 1.0 * np.cos(xx / (W / 7.0)) + rng.normal(0, 0.2, (H, W))
+    return np.ascontiguousarray(np.stack([u, v], -1).astype(np.float32))
+
+
+def flow_leg(args):
+    import torch
+    from PIL import Image
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import flow_vis_restate as F
+    from vps_amd import flowvis, hip, nhwc
+    assert torch.cuda.is_available(), 'the flow colour kernels need the MI355X'
+    dev = torch.device('cuda:0')
+    H, W, Q, LD = args.height, args.width, 90, 4
+    fields = [flow_field(H, W, s) for s in range(4)]
+    maps = [nhwc.FMap(torch.from_numpy(F.strided(f, LD, 0, 0.0)).to(dev)[None].contiguous(), 2, 0) for f in fields]
+    rep = dict(mode='flow_output', size=[H, W], frames=args.frames, flow_pixel_stride=LD, quality=Q, host_cpus=os.cpu_count(), csrc_sha16=hip.csrc_sha16())
+
+    def timed(fn):
+        for _ in range(3):
+            fn(0)
+        torch.cuda.synchronize()
+        ms = []
+        for i in range(30):
+            e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
+            e0.record()
+            fn(i)
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return float(np.median(ms)), float(min(ms))
+
+    rad = torch.empty(1, dtype=torch.float64, device=dev)
+    rgb = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+    lib = hip.load()
+    med, mn = timed(lambda i: flowvis.flow_max_radius(maps[i % 4], rad))
+    alg = H * W * LD * 4
+    rep['max_radius'] = dict(device_ms_median_of_30=round(med, 4), device_ms_min=round(mn, 4), algorithmic_MB=round(alg / 1e6, 2),
+                             fraction_of_8TBps=round(alg / (med * 1e-3) / 8e12, 4), note='includes the 8-byte memset the call enqueues')
+    flowvis.flow_max_radius(maps[1], rad)
+    med, mn = timed(lambda i: hip.check(lib.vps_flow_colour(maps[i % 4].ptr(), LD, 0, H, W, hip.ptr(rad), hip.ptr(rgb), hip.stream_ptr()), 'vps_flow_colour'))
+    alg = H * W * LD * 4 + H * W * 3
+    rep['colour'] = dict(device_ms_median_of_30=round(med, 4), device_ms_min=round(mn, 4), algorithmic_MB=round(alg / 1e6, 2),
+                         fraction_of_8TBps=round(alg / (med * 1e-3) / 8e12, 4))
+    got = flowvis.flow_colour(maps[1]).cpu().numpy()
+    assert np.array_equal(got, F.colour(fields[1])), 'the device image is not the restatement\'s'
+    rep['image_equal_to_numpy_restatement'] = True
+
+    def run_device(fmt, workers):
+        w = flowvis.FlowWriter(dev, workers=workers, slots=8, fmt=fmt, quality=Q)
+        with tempfile.TemporaryDirectory() as tmp:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for f in range(args.frames):
+                w.submit(maps[f % 4], os.path.join(tmp, '%04d.%s' % (f, fmt)))
+            t_submit = time.perf_counter() - t0
+            w.close()
+            dt = time.perf_counter() - t0
+        assert w.written == args.frames
+        return dict(frames_per_s=round(args.frames / dt, 1), submit_s=round(t_submit, 4), total_s=round(dt, 4), MB_written=round(w.bytes_written / 1e6, 2))
+
+    def run_host(fmt, workers):
+        from concurrent.futures import ThreadPoolExecutor
+
+        def job(flow, name):
+            if fmt == 'flo':
+                with open(name, 'wb') as fh:
+                    fh.write(flowvis._flo_header(H, W))
+                    flow.tofile(fh)
+            else:
+                Image.fromarray(F.colour(flow)).save(name, format='JPEG', quality=Q, subsampling=2, optimize=False)
+            return os.path.getsize(name)
+        with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(workers) as pool:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            futs = []
+            for f in range(args.frames):
+                m = maps[f % 4]                                      # the download the host path needs: the two flow channels, 16.8 MB
+                flow = m.t[0, :, :, m.coff:m.coff + 2].contiguous().cpu().numpy()
+                futs.append(pool.submit(job, flow, os.path.join(tmp, '%04d.%s' % (f, fmt))))
+            t_submit = time.perf_counter() - t0
+            nbytes = sum(x.result() for x in futs)
+            dt = time.perf_counter() - t0
+        return dict(frames_per_s=round(args.frames / dt, 1), submit_s=round(t_submit, 4), total_s=round(dt, 4), MB_written=round(nbytes / 1e6, 2))
+
+    def repeated(fn, fmt, workers):
+        """`args.repeats` windows of `args.frames` frames: the median window, with the spread of the rate over the windows"""
+        runs = sorted((fn(fmt, workers) for _ in range(args.repeats)), key=lambda r: r['frames_per_s'])
+        return dict(runs[len(runs) // 2], frames_per_s_min=runs[0]['frames_per_s'], frames_per_s_max=runs[-1]['frames_per_s'], windows=len(runs))
+
+    rep['repeats'] = args.repeats
+    for fmt in ('jpg', 'flo'):
+        run_device(fmt, 2)                                           # warm-up: ring slots, pinned staging, copy streams
+        rep['device_writer_' + fmt] = {str(n): repeated(run_device, fmt, n) for n in (1, 2, 4)}
+        rep['host_numpy_' + fmt] = {str(n): repeated(run_host, fmt, n) for n in (1, 2, 4)}
+        rep['verdict_' + fmt] = {str(n): ('device path %s: %.1f vs %.1f frames/s' % (
+            'wins' if rep['device_writer_' + fmt][str(n)]['frames_per_s'] > rep['host_numpy_' + fmt][str(n)]['frames_per_s'] else 'LOSES',
+            rep['device_writer_' + fmt][str(n)]['frames_per_s'], rep['host_numpy_' + fmt][str(n)]['frames_per_s'])) for n in (1, 2, 4)}
+    rep['not_measured'] = "the 'png' format; a clip of the detector with keep_flow and --flow against the same clip without them"
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--leg', default='png', choices=['png', 'overlay'])
+    ap.add_argument('--leg', default='png', choices=['png', 'overlay', 'flow'])
     ap.add_argument('--frames', type=int, default=30)
+    ap.add_argument('--repeats', type=int, default=3, help='--leg flow: windows of --frames frames per writer figure (median and spread are reported)')
     ap.add_argument('--height', type=int, default=1024)
     ap.add_argument('--width', type=int, default=2048)
-    ap.add_argument('--out', default=None, help='default: profiles/png_output_pipeline.json, or profiles/overlay_output_pipeline.json for --leg overlay')
+    ap.add_argument('--out', default=None, help='default: profiles/<png|overlay|flow>_output_pipeline.json by --leg')
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, 'profiles', 'png_output_pipeline.json' if args.leg == 'png' else 'overlay_output_pipeline.json')
-    if args.leg == 'overlay':
-        line = json.dumps(overlay_leg(args))
+        args.out = os.path.join(ROOT, 'profiles', {'png': 'png_output_pipeline.json', 'overlay': 'overlay_output_pipeline.json',
+                                                   'flow': 'flow_output_pipeline.json'}[args.leg])
+    if args.leg in ('overlay', 'flow'):
+        line = json.dumps(overlay_leg(args) if args.leg == 'overlay' else flow_leg(args))
         print(line)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

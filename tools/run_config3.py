@@ -55,6 +55,9 @@ def parse_args(argv=None):
                     'keeps every decoded frame on the device until the maps are unified, 6 MB per frame at 1024x2048)')
     ap.add_argument('--overlay-quality', type=int, default=90)
     ap.add_argument('--overlay-alpha', type=int, default=128, help='weight of the colour map, 0..256')
+    ap.add_argument('--flow', default=None, metavar='DIR', help='write DIR/<name>.<ext> for every frame: the FlowNet2 flow of the frame (off by default)')
+    ap.add_argument('--flow-format', default='jpg', choices=['jpg', 'png', 'flo'], help='colour image (jpg, png) or the raw Middlebury field (flo)')
+    ap.add_argument('--flow-max-rad', type=float, default=None, metavar='X', help='one normaliser of the flow colours for all frames (default: each frame its own maximum)')
     ap.add_argument('--dry-run', action='store_true')
     ap.add_argument('--dry-size', default='128x256'); ap.add_argument('--dry-videos', type=int, default=1); ap.add_argument('--dry-frames', type=int, default=16)
     ap.add_argument('--check-only', action='store_true')
@@ -159,6 +162,11 @@ def run(args, tmp):
     files = [os.path.join(img_prefix, x['file_name']) for x in info]
     feeder = ClipFeeder(files, prep, workers=args.png_workers, keep_frames=bool(args.overlay)).start()
     res = dict(all_names=[], all_ssegs=[], all_panos=[], all_pano_cls_inds=[], all_pano_obj_ids=[], all_frames=[])
+    flow_writer = None
+    if args.flow:
+        from vps_amd.flowvis import FlowWriter, flow_name
+        model.keep_flow = True
+        flow_writer = FlowWriter(dev, fmt=args.flow_format, max_rad=args.flow_max_rad)
     t0 = time.perf_counter()
     with torch.no_grad():
         for idx, im in enumerate(info):
@@ -175,7 +183,12 @@ def run(args, tmp):
             res['all_names'].append(os.path.basename(files[idx]))
             if args.overlay:
                 res['all_frames'].append(feeder.frame(idx))       # the decoded BGR frame the feeder holds anyway
+            if flow_writer is not None:
+                flow_writer.submit(result[2]['flow'], flow_name(args.flow, files[idx], args.flow_format))
     torch.cuda.synchronize()
+    if flow_writer is not None:
+        flow_files = flow_writer.close()
+        report['flow'] = dict(dir=args.flow, files=len(flow_files), format=args.flow_format, max_rad=args.flow_max_rad, bytes=flow_writer.bytes_written)
     dt = time.perf_counter() - t0
     feeder.close()
     # ---- test_vpq.py:150-198 ------------------------------------------------------------------------------------------------------

@@ -54,8 +54,9 @@ def uint8_frame(H, W, seed, shift):
     return synth.synth_frame(H, W, seed=seed, shift=shift, noise=2.0 if shift != (0, 0) else 0.0).astype(np.uint8)
 
 
-def run_model(prec, videos, nframes, H, W, dev, separated=False):
-    """test_vpq.py:129-149 + single_gpu_test (:28-69) on `videos` synthetic clips -> pano_results with DEVICE maps"""
+def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None):
+    """test_vpq.py:129-149 + single_gpu_test (:28-69) on `videos` synthetic clips -> pano_results with DEVICE maps.
+    `flow` = (directory, format, max_rad): the FlowNet2 flow of EVERY frame as DIR/<name>.<format> (flowvis.FlowWriter)"""
     import vps_amd
     from vps_amd import nhwc, synth
     from vps_amd.pipeline import DeviceImagePrep, PairFeeder
@@ -71,7 +72,12 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False):
         nhwc.DEFAULT_PREC = old
     prep = DeviceImagePrep(**cfg.img_norm_cfg, size_divisor=32, img_scale=(max(H, W), min(H, W)), device=dev)
     feed = PairFeeder(prep)
-    res = dict(all_names=[], all_ssegs=[], all_panos=[], all_pano_cls_inds=[], all_pano_obj_ids=[], all_frames=[])
+    res = dict(all_names=[], all_ssegs=[], all_panos=[], all_pano_cls_inds=[], all_pano_obj_ids=[], all_frames=[], flow_files=[])
+    flow_writer = None
+    if flow:
+        from vps_amd.flowvis import FlowWriter, flow_name
+        model.keep_flow = True
+        flow_writer = FlowWriter(dev, fmt=flow[1], max_rad=flow[2])
     decoded = [[uint8_frame(H, W, seed=v, shift=(2 * f, f)) for f in range(nframes)] for v in range(videos)]   # "cv2.imread" results (BGR uint8)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -90,6 +96,10 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False):
             res['all_pano_obj_ids'].append(result[2]['panoptic_det_obj_ids'].cpu().numpy())
             res['all_names'].append(name)
             res['all_frames'].append(decoded[v][f])                                # the decoded frame itself: what --overlay draws on
+            if flow_writer is not None:
+                flow_writer.submit(result[2]['flow'], flow_name(flow[0], name, flow[1]))
+    if flow_writer is not None:
+        res['flow_files'] = flow_writer.close()
     torch.cuda.synchronize()
     return res, time.perf_counter() - t0
 
@@ -153,12 +163,16 @@ def main():
     ap.add_argument('--overlay', default=None, metavar='DIR', help='write DIR/<name>.jpg for every frame: the panoptic result blended over the frame (off by default)')
     ap.add_argument('--overlay-quality', type=int, default=90)
     ap.add_argument('--overlay-alpha', type=int, default=128, help='weight of the colour map, 0..256')
+    ap.add_argument('--flow', default=None, metavar='DIR', help='write DIR/<name>.<ext> for every frame: the FlowNet2 flow of the frame (off by default)')
+    ap.add_argument('--flow-format', default='jpg', choices=['jpg', 'png', 'flo'], help='colour image (jpg, png) or the raw Middlebury field (flo)')
+    ap.add_argument('--flow-max-rad', type=float, default=None, metavar='X', help='one normaliser of the flow colours for all frames (default: each frame its own maximum)')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     labeled_fid, lambda_ = 20, 5
     overlay = (args.overlay, args.overlay_quality, args.overlay_alpha) if args.overlay else None
     nper = len(range(labeled_fid // lambda_, args.frames, lambda_))
-    res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated)
+    flow = (args.flow, args.flow_format, args.flow_max_rad) if args.flow else None
+    res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated, flow)
     t0 = time.perf_counter()
     names, pans, pj = postprocess(res, os.path.join(args.out, 'pred'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png, overlay)
     dpost = time.perf_counter() - t0
@@ -173,7 +187,8 @@ def main():
     deval = time.perf_counter() - t0
     files = sorted(os.listdir(os.path.join(args.out, 'pred', 'pan_pred')))
     report = dict(videos=args.videos, frames_per_video=args.frames, size=[args.height, args.width], prec=args.prec, gt=args.gt_prec or 'self', weights='synthetic seed 0' + (' + separated fc_cls' if args.separated else ''),
-                  labelled_frames=len(names), png_files=len(files), overlay_files=len(os.listdir(args.overlay)) if args.overlay else 0, vpq=round(score['vpq'], 4),
+                  labelled_frames=len(names), png_files=len(files), overlay_files=len(os.listdir(args.overlay)) if args.overlay else 0,
+                  flow_files=len(res['flow_files']), vpq=round(score['vpq'], 4),
                   pq_per_window={str(k): round(100 * score[k]['pq'], 4) for k in (1, 2, 3, 4)},
                   seconds=dict(model=round(dt, 3), postprocess_and_png=round(dpost, 3), eval=round(deval, 3)),
                   frames_per_s_upload_prep_model_sequential=round(args.videos * args.frames / dt, 2))

@@ -13,6 +13,7 @@ from . import backbones, necks, heads, flownet2, panoptic_ops, detector  # noqa:
 from .detector import PanopticFuse, PanopticFuseTrack, PanopticTrack  # noqa: F401,E402
 from .checkpoint import load_checkpoint  # noqa: F401,E402
 from . import ipq  # noqa: F401,E402  (image-level evaluation: SemanticEvaluator, ImagePanopticUnifier, ImageConverter, pq_compute, evaluate_panoptic)
+from . import flowvis  # noqa: F401,E402  (optical-flow output: flow_colour, FlowWriter, write_flo / read_flo)
 from .dataloader import DataContainer, LookaheadLoader, MMDataParallel, build_dataloader  # noqa: F401,E402
 
 __version__ = '0.1.0'

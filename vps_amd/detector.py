@@ -62,6 +62,7 @@ def bbox2result_with_id(bboxes, labels, obj_ids, num_classes):
 class PanopticFuseTrack(HipModule):
     # the two sibling detectors of the reference reuse this class with one branch switched off (bottom of the file)
     with_fusion = True        # FlowNet2 + flow-guided BFP-TCEA temporal fusion neck (panoptic_fusetrack.py:506-518)
+    keep_flow = False         # True: pano_results['flow'] = the frame's full-resolution FlowNet2 flow, device fp32 [h,w,2] (flowvis.py)
     with_track = True         # TrackHead + instance-id assignment (panoptic_fusetrack.py:400-469)
 
     def __init__(self, backbone, rpn_head, bbox_roi_extractor, bbox_head, mask_roi_extractor, mask_head, train_cfg,
@@ -233,6 +234,9 @@ class PanopticFuseTrack(HipModule):
         return self._simple_test_guarded(img, img_meta, proposals, rescale, ref_img, inject, ref_feature, defer_tracking, prefetch)
 
     def _simple_test_guarded(self, img, img_meta, proposals, rescale, ref_img, inject, ref_feature, defer_tracking, prefetch):
+        if self.keep_flow and (not self.with_fusion or (inject is not None and 'neck_out' in inject)):
+            raise hip.VpsHipError('keep_flow: %s computes no optical flow (no FlowNet2 on its path)'
+                                  % (type(self).__name__ if not self.with_fusion else 'a frame with an injected neck output'))
         if img.is_cuda:
             self.ensure_packed(img.device)      # a lazily packed model registers its f16x3 layers here: `guard` must see them
         guard = nhwc._F16_NEXT[0] > 1 and img.is_cuda
@@ -317,7 +321,7 @@ class PanopticFuseTrack(HipModule):
             if self._side is None or self._side.device != dev:
                 self._side = torch.cuda.Stream(device=dev)
             side = self._side
-        flow = cat = aux = levels = None
+        flow = cat = aux = levels = kept_flow = None
         late = []
         if inject is not None and 'neck_out' in inject:
             # tests: the neck output itself is injected (five NCHW levels) — the image-only stages and the neck are skipped
@@ -385,6 +389,10 @@ class PanopticFuseTrack(HipModule):
             C = self.extra_neck.in_channels
             # flowR2T = F.interpolate(flow, 0.25, bilinear) * 0.25 written straight into the LiteFlowNet input buffer
             nhwc.resize(flow, cat.window(C + 81, 2), 'bilinear', 0.25)
+            if self.keep_flow:
+                # a copy of its own, made on the frame's stream: the flow lives in a ring workspace that the frame after next rewrites.
+                # Cropped to the image: without the Pad-to-32 rows (FlowNet2.run has already trimmed its own 64-multiple padding)
+                kept_flow = flow.t[0, :meta['img_shape'][0], :meta['img_shape'][1], flow.coff:flow.coff + 2].clone(memory_format=torch.contiguous_format)
             self._mark('backbone_fpn')
             # reference-frame gathered feature: cached from the previous call when the frames are consecutive
             cache = self._cache
@@ -518,6 +526,8 @@ class PanopticFuseTrack(HipModule):
             pano_results['panoptic_det_labels'] = det_labels[keep_t]
             ids_t = det['ids_dev'][:K].long() if has_ids else torch.full((K,), -1, dtype=torch.long, device=dev)
             pano_results['panoptic_det_obj_ids'] = ids_t[keep_t]
+        if self.keep_flow:
+            pano_results['flow'] = kept_flow
         self._track_record = dict(det_bboxes=det_bboxes, det_labels=det_labels, cls_prob=cls_prob, emb=det['emb'],
                                   keep_inds=keep_inds)
         self._aux = dict(flow=flow, levels=levels, cat=cat, neck_out=x, neck_aux=aux, fcn_score=fcn_score, det=det,

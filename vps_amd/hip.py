@@ -33,6 +33,7 @@ SYMBOLS = [
     'vps_png_inflate', 'vps_png_reconstruct_ws', 'vps_png_reconstruct', 'vps_png_reconstruct_block_rows',
     'vps_unify_tables_image', 'vps_segment_stats_ch', 'vps_segment_paint_ch', 'vps_sseg_confusion',
     'vps_overlay_render', 'vps_jpeg_quant_tables', 'vps_jpeg_encode_bound', 'vps_jpeg_encode_coef', 'vps_jpeg_write_bound', 'vps_jpeg_write',
+    'vps_flow_max_radius', 'vps_flow_colour',
 ]
 
 
@@ -203,6 +204,8 @@ def load():
                                          c_void_p]
     lib.vps_overlay_render.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.vps_jpeg_encode_coef.argtypes = [c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.vps_flow_max_radius.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+    lib.vps_flow_colour.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.vps_png_reconstruct_ws.argtypes = [c_int, c_int, c_int, POINTER(c_int64)]
     lib.vps_png_reconstruct.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]
     lib.vps_png_reconstruct_block_rows.argtypes = []
