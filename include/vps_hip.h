@@ -588,6 +588,38 @@ int vps_png_deflate(const uint8_t* img, int H, int W, int channels, int64_t row_
 int vps_flow_max_radius(const float* flow, int ld, int coff, int H, int W, double* out, void* stream);
 int vps_flow_colour(const float* flow, int ld, int coff, int H, int W, const double* max_rad, uint8_t* rgb, void* stream);
 
+/* Track tubes (csrc/rle_ops.hip, csrc/rle_host.cpp; vps_amd/tubes.py): the COCO run-length encoding of every
+ * segment of a panoptic map. The device lists the runs of the map, the host turns the list into one `counts` string per segment.
+ *
+ * vps_rle_runs: pan_2ch DEVICE uint8 [H][W][3]; key = pan_2ch[.., 0] * 256 + pan_2ch[.., id_channel], id_channel 1 or 2 (as
+ * vps_segment_stats_ch). Position q = x * H + y (column-major, the order of COCO's rleEncode). A run starts at q = 0 and wherever
+ * key(q) != key(q - 1); a run that leaves a column at its bottom and goes on at the top of the next one is ONE run.
+ *   run_start  DEVICE uint32 [cap] (4-byte aligned), run_key DEVICE uint16 [cap]: the first min(nruns, cap) runs in ascending q;
+ *              nothing is stored at or behind index cap
+ *   nruns      DEVICE int32 [1]: the TRUE number of runs, also when it exceeds cap (the caller then calls again with that capacity)
+ *   ws         DEVICE workspace, 16-byte aligned, at least vps_rle_runs_ws(H, W) bytes (0 for sizes that are rejected)
+ * Three launches on `stream`, no sync, no hidden allocation, no atomics: the list is the same on every call. Rejected before any
+ * launch (<= -1000): a null pointer, H or W < 1, H * W >= 2^31, id_channel not 1 or 2, cap < 0, a short or misaligned workspace.
+ * vps_rle_band_rows: rows of one band of the kernel's sweeps (its launch constant; for tests that put a run across a band edge).
+ *
+ * vps_rle_strings (HOST arithmetic only, no allocation, thread-safe): run list -> compressed COCO `counts` strings.
+ *   run_start, run_key, nruns  HOST copies of the list (all nruns runs), npix = H * W
+ *   keys       sorted ascending, unique, nkeys of them; a key that is absent gets the single count npix
+ *   out        the strings one behind the other, no terminator: key i at out + offset[i], length[i] characters (offset, length
+ *              int64 [nkeys]); vps_rle_strings_bound(nruns, nkeys) characters always suffice
+ *   scratch    int64 [4 * nkeys]
+ * The counts of a key alternate zero-runs and one-runs, starting with a zero-run that may be 0; a trailing zero-run is written only
+ * when it is not empty. Coding: COCO's rleToString (count i >= 3 as the difference to count i - 2; 5 bits and a continuation bit per
+ * character, + 48). Too small an out_capacity: -1008, offset / length hold what is needed, nothing is stored to out. A list that does
+ * not start at 0, does not ascend, reaches npix or repeats a key in neighbouring runs, and unsorted keys, are rejected too. */
+int vps_rle_runs(const uint8_t* pan_2ch, int H, int W, int id_channel, uint32_t* run_start, uint16_t* run_key, int cap, int32_t* nruns,
+                 void* ws, size_t ws_bytes, void* stream);
+int64_t vps_rle_runs_ws(int H, int W);
+int vps_rle_band_rows(void);
+int vps_rle_strings(const uint32_t* run_start, const uint16_t* run_key, int nruns, int64_t npix, const uint16_t* keys, int nkeys, char* out,
+                    int64_t out_capacity, int64_t* offset, int64_t* length, int64_t* scratch);
+int64_t vps_rle_strings_bound(int nruns, int nkeys);
+
 /* ----------------------------------------------------------------------------------------------
  * Input preparation: Normalize -> Pad(size_divisor) -> ImageToTensor of the test pipeline in one pass.
  * Replaces mmdet/datasets/pipelines/transforms.py:258-269, :310-318 and formating.py:52-67 (mmcv 0.2.14 imnormalize,

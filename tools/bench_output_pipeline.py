@@ -28,7 +28,16 @@ plus noise) in FlowNet2's layout (NHWC, pixel stride 4), one file per frame.
                  8 TB/s (the whole strided map read - the 16-byte pixels share cache lines with their padding; colour: + the image written)
   frames/s       `FlowWriter` at 1, 2 and 4 workers for 'jpg' and 'flo' against the host way on as many threads: download the two flow
                  channels (16.8 MB), the NumPy restatement of the colour coding (tests/flow_vis_restate.py) + PIL save for 'jpg', header
-                 + `tofile` for 'flo'; each figure is the median of --repeats windows of --frames frames, with the slowest and fastest"""
+                 + `tofile` for 'flo'; each figure is the median of --repeats windows of --frames frames, with the slowest and fastest
+
+`--leg tubes` measures the track tubes (and writes profiles/tubes_output_pipeline.json): the `pan_2ch` maps of above (45 instances), the
+COCO encoding of every instance of every frame.
+  device_ms      one `vps_rle_runs` call (two sweeps and the scan), the median of 30, timed with events; the maps are 6 MB each and
+                 stay in the caches between calls, so the figure is a cache-resident one; the run count and the bytes downloaded
+  host_ms        `vps_rle_strings` on one thread for one frame's run list, the median of 30
+  frames/s       `TubeCollector` (things by class) at 1, 2 and 4 coding threads against the host way on as many threads: download
+                 `pan_2ch` (6.3 MB), `pan == key` per instance, the NumPy restatement of rleEncode + rleToString (tests/rle_restate.py;
+                 pycocotools where it is installed); each figure is the median of --repeats windows of --frames frames"""
 import argparse
 import io
 import json
@@ -299,20 +308,129 @@ def flow_leg(args):
     return rep
 
 
+def tubes_leg(args):
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import rle_restate as R
+    from vps_amd import hip, tubes
+    assert torch.cuda.is_available(), 'vps_rle_runs needs the MI355X'
+    dev = torch.device('cuda:0')
+    H, W, LAST_STUFF = args.height, args.width, 10
+    twos = [label_map(H, W, s) for s in range(4)]
+    maps = [torch.from_numpy(t).to(dev) for t in twos]
+    try:
+        import pycocotools.mask as cm
+    except ImportError:
+        cm = None
+    rep = dict(mode='tubes_output', size=[H, W], frames=args.frames, repeats=args.repeats, host_cpus=os.cpu_count(), csrc_sha16=hip.csrc_sha16(),
+               host_encoder='pycocotools' if cm is not None else 'NumPy restatement (tests/rle_restate.py)')
+    lib = hip.load()
+    cap = H * W // 8
+    rs = torch.empty(cap, dtype=torch.int32, device=dev)
+    rk = torch.empty(cap, dtype=torch.int16, device=dev)
+    nr = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(tubes.rle_runs_ws(H, W), dtype=torch.uint8, device=dev)
+
+    def launch(i):
+        hip.check(lib.vps_rle_runs(hip.ptr(maps[i % 4]), H, W, 2, hip.ptr(rs), hip.ptr(rk), cap, hip.ptr(nr), hip.ptr(ws), ws.numel(), hip.stream_ptr()),
+                  'vps_rle_runs')
+    for i in range(3):
+        launch(i)
+    torch.cuda.synchronize()
+    ms = []
+    for i in range(30):
+        e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
+        e0.record()
+        launch(i)
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    launch(1)
+    n = int(nr.item())
+    alg = 2 * (H * W * 2) + 2 * ws.numel() + n * 6                   # two sweeps over two channels, the cells written and scanned, the list
+    rep['rle_runs'] = dict(device_ms_median_of_30=round(float(np.median(ms)), 4), device_ms_min=round(float(min(ms)), 4), launches=3, runs=n,
+                           downloaded_bytes=n * 6, map_bytes=H * W * 3, algorithmic_MB=round(alg / 1e6, 2),
+                           inputs='cache-resident: four 6.3 MB maps cycled', timed_with='events around the three launches of one call')
+    start, key = tubes.runs_to_host(rs[:n], rk[:n])
+    want_start, want_key = R.runs_of(R.key_map(twos[1], 2))
+    assert np.array_equal(start, want_start) and np.array_equal(key, want_key), 'the run list is not the restatement\'s'
+    keys = tubes.default_keys(key)
+    keys = keys[(keys >> 8) > LAST_STUFF]
+    hs = []
+    for _ in range(33):
+        t0 = time.perf_counter()
+        strings = tubes.rle_strings(start, key, H * W, keys)
+        hs.append((time.perf_counter() - t0) * 1e3)
+    km = R.key_map(twos[1], 2)
+    assert all(s == R.encode(km == k)['counts'].encode('ascii') for k, s in zip(keys[:5], strings)), 'the strings are not the restatement\'s'
+    rep['rle_strings'] = dict(host_ms_median_of_30=round(float(np.median(hs[3:])), 4), host_ms_min=round(float(min(hs[3:])), 4), threads=1, keys=int(keys.size),
+                              string_bytes=int(sum(len(s) for s in strings)))
+    rep['equal_to_numpy_restatement'] = True
+
+    def run_device(workers):
+        col = tubes.TubeCollector(things_only=True, id_last_stuff=LAST_STUFF, workers=workers, device=dev)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for f in range(args.frames):
+            col.add(0, '%04d.png' % f, maps[f % 4])
+        t_add = time.perf_counter() - t0
+        res = col.result()
+        dt = time.perf_counter() - t0
+        col.close()
+        return dict(frames_per_s=round(args.frames / dt, 1), add_s=round(t_add, 4), total_s=round(dt, 4), tracks=len(res['videos'][0]['tracks']))
+
+    def host_frame(two):
+        km = two[..., 0].astype(np.int32) * 256 + two[..., 2]
+        out = {}
+        for k in np.unique(km):
+            if (k >> 8) == 255 or (k >> 8) <= LAST_STUFF:
+                continue
+            mask = km == k
+            if cm is not None:
+                out[int(k)] = cm.encode(np.asfortranarray(mask.astype(np.uint8)))
+            else:
+                out[int(k)] = R.encode(mask)
+        return len(out)
+
+    def run_host(workers):
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(workers) as pool:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            futs = [pool.submit(host_frame, maps[f % 4].cpu().numpy()) for f in range(args.frames)]     # the 6.3 MB download the host way needs
+            t_add = time.perf_counter() - t0
+            ntr = [x.result() for x in futs]
+            dt = time.perf_counter() - t0
+        return dict(frames_per_s=round(args.frames / dt, 1), add_s=round(t_add, 4), total_s=round(dt, 4), masks_per_frame=ntr[0])
+
+    def repeated(fn, workers):
+        runs = sorted((fn(workers) for _ in range(args.repeats)), key=lambda r: r['frames_per_s'])
+        return dict(runs[len(runs) // 2], frames_per_s_min=runs[0]['frames_per_s'], frames_per_s_max=runs[-1]['frames_per_s'], windows=len(runs))
+
+    run_device(2)                                                    # warm-up: the statistics table, the allocator's blocks
+    rep['tube_collector'] = {str(w): repeated(run_device, w) for w in (1, 2, 4)}
+    rep['host_numpy'] = {str(w): repeated(run_host, w) for w in (1, 2, 4)}
+    rep['verdict'] = {str(w): ('device path %s: %.1f vs %.1f frames/s' % (
+        'wins' if rep['tube_collector'][str(w)]['frames_per_s'] > rep['host_numpy'][str(w)]['frames_per_s'] else 'LOSES',
+        rep['tube_collector'][str(w)]['frames_per_s'], rep['host_numpy'][str(w)]['frames_per_s'])) for w in (1, 2, 4)}
+    rep['not_measured'] = 'kernel times from a profiler trace; maps that are not cache-resident; a detector clip with --tubes against the same clip without'
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--leg', default='png', choices=['png', 'overlay', 'flow'])
+    ap.add_argument('--leg', default='png', choices=['png', 'overlay', 'flow', 'tubes'])
     ap.add_argument('--frames', type=int, default=30)
-    ap.add_argument('--repeats', type=int, default=3, help='--leg flow: windows of --frames frames per writer figure (median and spread are reported)')
+    ap.add_argument('--repeats', type=int, default=3, help='--leg flow / tubes: windows of --frames frames per writer figure (median and spread are reported)')
     ap.add_argument('--height', type=int, default=1024)
     ap.add_argument('--width', type=int, default=2048)
-    ap.add_argument('--out', default=None, help='default: profiles/<png|overlay|flow>_output_pipeline.json by --leg')
+    ap.add_argument('--out', default=None, help='default: profiles/<png|overlay|flow|tubes>_output_pipeline.json by --leg')
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(ROOT, 'profiles', {'png': 'png_output_pipeline.json', 'overlay': 'overlay_output_pipeline.json',
-                                                   'flow': 'flow_output_pipeline.json'}[args.leg])
-    if args.leg in ('overlay', 'flow'):
-        line = json.dumps(overlay_leg(args) if args.leg == 'overlay' else flow_leg(args))
+                                                   'flow': 'flow_output_pipeline.json', 'tubes': 'tubes_output_pipeline.json'}[args.leg])
+    if args.leg in ('overlay', 'flow', 'tubes'):
+        line = json.dumps({'overlay': overlay_leg, 'flow': flow_leg, 'tubes': tubes_leg}[args.leg](args))
         print(line)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -58,6 +58,8 @@ def parse_args(argv=None):
     ap.add_argument('--flow', default=None, metavar='DIR', help='write DIR/<name>.<ext> for every frame: the FlowNet2 flow of the frame (off by default)')
     ap.add_argument('--flow-format', default='jpg', choices=['jpg', 'png', 'flo'], help='colour image (jpg, png) or the raw Middlebury field (flo)')
     ap.add_argument('--flow-max-rad', type=float, default=None, metavar='X', help='one normaliser of the flow colours for all frames (default: each frame its own maximum)')
+    ap.add_argument('--tubes', action='store_true', help='write tubes.json beside pred.json: the COCO run-length encoding, box and area of every tracked instance in '
+                    'every labelled frame (vps_amd.tubes; off by default)')
     ap.add_argument('--dry-run', action='store_true')
     ap.add_argument('--dry-size', default='128x256'); ap.add_argument('--dry-videos', type=int, default=1); ap.add_argument('--dry-frames', type=int, default=16)
     ap.add_argument('--check-only', action='store_true')
@@ -209,9 +211,16 @@ def run(args, tmp):
     if args.device_png:
         from vps_amd.postprocess import DevicePngWriter
         kw['writer'] = DevicePngWriter(dev)
+    if args.tubes:
+        from vps_amd.tubes import TubeCollector
+        kw['tubes'] = TubeCollector(things_only=True, device=dev, id_last_stuff=unifier.id_last_stuff)
     pans, pj = inference_panoptic_video(pred_pans_2ch, output_dir, categories, names, n_video=args.n_video, color_generator=gen, device=dev, **kw)
     if args.device_png:
         kw['writer'].close()
+    if args.tubes:
+        tb = kw['tubes'].result()
+        report['tubes'] = dict(file=os.path.join(output_dir, 'tubes.json'), videos=len(tb['videos']), tracks=sum(len(v['tracks']) for v in tb['videos']))
+        kw['tubes'].close()
     if args.overlay:
         from run_vps_synthetic import ColorGenerator
         from vps_amd.postprocess import write_overlays

@@ -36,6 +36,8 @@ def parse_args(argv=None):
     ap.add_argument('--out', default='work_dirs/cityscapes/fuse_vpct/val.pkl')
     ap.add_argument('--stuff-area-limit', type=int, default=2048, help='configs/cityscapes/test_cityscapes_1gpu.yaml:29')
     ap.add_argument('--prec', default='f16x3', choices=['f32', 'bf16x6', 'f16x3'])
+    ap.add_argument('--tubes', action='store_true', help='write <out>_pans_unified/tubes.json: the COCO run-length encoding, box and area of every instance of every '
+                    'image (vps_amd.tubes; one "video" of one frame per image; off by default)')
     ap.add_argument('--dry-run', action='store_true')
     ap.add_argument('--height', type=int, default=128); ap.add_argument('--width', type=int, default=256)
     ap.add_argument('--dry-images', type=int, default=3)
@@ -159,6 +161,13 @@ def run(args, tmp):
     pred_pans_2ch = [two[k] for k in sorted(two)]
     ipq.evaluate_panoptic(pred_pans_2ch, args.out.replace('.pkl', '_pans_unified'), gt_file, os.path.join(args.data_root, 'panoptic'),
                           None, color_generator(categories), device=dev)
+    if args.tubes:
+        from vps_amd.tubes import TubeCollector
+        col = TubeCollector(things_only=True, id_channel=1, device=dev)       # image-level maps: the instance id is pan_ins, 0 for stuff
+        for i, name in enumerate(sorted(two)):
+            col.add(i, name, two[name])
+        col.write(os.path.join(args.out.replace('.pkl', '_pans_unified'), 'tubes.json'))
+        col.close()
     return 0
 
 

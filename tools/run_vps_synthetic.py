@@ -104,10 +104,11 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None):
     return res, time.perf_counter() - t0
 
 
-def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_png=False, overlay=None):
+def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_png=False, overlay=None, tubes=False):
     """test_vpq.py:178-198 with the device-side unifier / converter / asynchronous writer (`device_png`: the PNGs are filtered and
     deflated on the device too, postprocess.DevicePngWriter). `overlay` = (directory, quality, alpha): an overlay JPEG of EVERY frame,
-    blended and transformed on the device (postprocess.write_overlays)"""
+    blended and transformed on the device (postprocess.write_overlays). `tubes`: tubes.json beside pred.json, the COCO run-length
+    encoding, box and area of every tracked instance in every labelled frame (vps_amd.tubes)"""
     from vps_amd.postprocess import DevicePngWriter, PanopticUnifier, inference_panoptic_video, write_overlays
     unifier = PanopticUnifier(dev, 19, 9)
     two = unifier.get_unified_pan_result(res['all_ssegs'], res['all_panos'], res['all_pano_cls_inds'], obj_ids=res['all_pano_obj_ids'],
@@ -117,8 +118,14 @@ def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_pn
     names = keys[(labeled_fid // lambda_)::lambda_]                               # names of the labelled frames (im_jsons['images'])
     cats = {c['id']: c for c in CATEGORIES}
     writer = DevicePngWriter(dev) if device_png else None
+    collector = None
+    if tubes:
+        from vps_amd.tubes import TubeCollector
+        collector = TubeCollector(things_only=True, device=dev, id_last_stuff=unifier.id_last_stuff)
     pans, pj = inference_panoptic_video(pred_pans_2ch, out_dir, CATEGORIES, names, n_video=videos, color_generator=ColorGenerator(cats), device=dev,
-                                        labeled_fid=labeled_fid, lambda_=lambda_, nframes_per_video=nper, writer=writer)
+                                        labeled_fid=labeled_fid, lambda_=lambda_, nframes_per_video=nper, writer=writer, tubes=collector)
+    if collector is not None:
+        collector.close()
     if writer is not None:
         writer.close()
     if overlay:
@@ -163,6 +170,7 @@ def main():
     ap.add_argument('--overlay', default=None, metavar='DIR', help='write DIR/<name>.jpg for every frame: the panoptic result blended over the frame (off by default)')
     ap.add_argument('--overlay-quality', type=int, default=90)
     ap.add_argument('--overlay-alpha', type=int, default=128, help='weight of the colour map, 0..256')
+    ap.add_argument('--tubes', action='store_true', help='write pred/tubes.json: run-length encoded masks, boxes and areas of every tracked instance (off by default)')
     ap.add_argument('--flow', default=None, metavar='DIR', help='write DIR/<name>.<ext> for every frame: the FlowNet2 flow of the frame (off by default)')
     ap.add_argument('--flow-format', default='jpg', choices=['jpg', 'png', 'flo'], help='colour image (jpg, png) or the raw Middlebury field (flo)')
     ap.add_argument('--flow-max-rad', type=float, default=None, metavar='X', help='one normaliser of the flow colours for all frames (default: each frame its own maximum)')
@@ -174,7 +182,7 @@ def main():
     flow = (args.flow, args.flow_format, args.flow_max_rad) if args.flow else None
     res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated, flow)
     t0 = time.perf_counter()
-    names, pans, pj = postprocess(res, os.path.join(args.out, 'pred'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png, overlay)
+    names, pans, pj = postprocess(res, os.path.join(args.out, 'pred'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png, overlay, args.tubes)
     dpost = time.perf_counter() - t0
     pred = (pans, pj)
     gt = pred

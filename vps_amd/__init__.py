@@ -14,6 +14,7 @@ from .detector import PanopticFuse, PanopticFuseTrack, PanopticTrack  # noqa: F4
 from .checkpoint import load_checkpoint  # noqa: F401,E402
 from . import ipq  # noqa: F401,E402  (image-level evaluation: SemanticEvaluator, ImagePanopticUnifier, ImageConverter, pq_compute, evaluate_panoptic)
 from . import flowvis  # noqa: F401,E402  (optical-flow output: flow_colour, FlowWriter, write_flo / read_flo)
+from . import tubes  # noqa: F401,E402  (track tubes: rle_runs, segment_rles, rle_decode, TubeCollector)
 from .dataloader import DataContainer, LookaheadLoader, MMDataParallel, build_dataloader  # noqa: F401,E402
 
 __version__ = '0.1.0'

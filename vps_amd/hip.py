@@ -34,6 +34,7 @@ SYMBOLS = [
     'vps_unify_tables_image', 'vps_segment_stats_ch', 'vps_segment_paint_ch', 'vps_sseg_confusion',
     'vps_overlay_render', 'vps_jpeg_quant_tables', 'vps_jpeg_encode_bound', 'vps_jpeg_encode_coef', 'vps_jpeg_write_bound', 'vps_jpeg_write',
     'vps_flow_max_radius', 'vps_flow_colour',
+    'vps_rle_runs', 'vps_rle_runs_ws', 'vps_rle_band_rows', 'vps_rle_strings', 'vps_rle_strings_bound',
 ]
 
 
@@ -93,7 +94,7 @@ def csrc_sha16():
 
 
 def load_host():
-    """the handle whose calls release the interpreter lock: the host-side functions (PNG decode / inflate, JPEG entropy decode and encode) that decode / writer threads run in parallel"""
+    """the handle whose calls release the interpreter lock: the host-side functions (PNG decode / inflate, JPEG entropy decode and encode, run lists to COCO strings) that decode / writer threads run in parallel"""
     load()
     return _host
 
@@ -200,6 +201,14 @@ def load():
         h.vps_jpeg_encode_bound.argtypes = [c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int64)]
         h.vps_jpeg_write_bound.argtypes = [c_int, c_int, c_int, POINTER(c_int64)]
         h.vps_jpeg_write.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, POINTER(c_int64)]
+        h.vps_rle_strings.restype = c_int
+        h.vps_rle_strings.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
+        h.vps_rle_strings_bound.restype = c_int64
+        h.vps_rle_strings_bound.argtypes = [c_int, c_int]
+    lib.vps_rle_runs.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]
+    lib.vps_rle_runs_ws.restype = c_int64
+    lib.vps_rle_runs_ws.argtypes = [c_int, c_int]
+    lib.vps_rle_band_rows.argtypes = []
     lib.vps_jpeg_reconstruct.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_int64, c_void_p,
                                          c_void_p]
     lib.vps_overlay_render.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]

@@ -128,6 +128,7 @@ class TrackConverter:
         lib = hip.load()
         annotations, pan_all, two_all = [], [], []
         inst2color = {}
+        self.frame_stats = []                                   # per frame (keys, rows) of the present segments, for tubes.TubeCollector
         for pan_2ch in pan_2ch_set:
             t = torch.from_numpy(np.ascontiguousarray(pan_2ch)) if isinstance(pan_2ch, np.ndarray) else pan_2ch
             t = t.to(self.device).contiguous()
@@ -138,6 +139,7 @@ class TrackConverter:
             keys = torch.nonzero(st[:, 0] > 0).flatten()
             rows = st[keys].cpu().numpy()                       # a few dozen present segments
             keys = keys.cpu().numpy()
+            self.frame_stats.append((keys, rows))
             seg, obj = keys >> 8, keys & 255
             order = np.argsort(1000 * seg + obj, kind='stable')  # np.unique(1000*seg + obj) ascending
             lut = np.zeros((65536, 3), dtype=np.uint8)
@@ -610,14 +612,16 @@ def png_name(save_folder, name):
 
 
 def inference_panoptic_video(pred_pans_2ch, output_dir, categories, names, n_video=0, color_generator=None, device='cuda',
-                             labeled_fid=20, lambda_=5, nframes_per_video=6, writer=None):
+                             labeled_fid=20, lambda_=5, nframes_per_video=6, writer=None, tubes=None):
     """`CityscapesVps.inference_panoptic_video` (cityscapes_vps.py:27-94) with the conversion on the device and asynchronous PNG
     writing: same arguments and return value `(pred_pans, pred_json)`, same files (`pan_2ch/`, `pan_pred/`, `pred.json`).
     `pred_pans_2ch`: per-frame uint8 [H,W,3] maps (host arrays or device tensors, e.g. straight from PanopticUnifier);
     `names`: the image file names of the SAMPLED frames (the reference passes them already sampled, test_vpq.py:186-197).
     color_generator: panopticapi's IdGenerator(categories) by default (imported lazily, like the reference); colours are handed
     out per video in the reference's order — one converter state per video, as `np.array_split(.., nprocs)` over whole videos
-    gives when nprocs == number of videos."""
+    gives when nprocs == number of videos.
+    tubes: a `tubes.TubeCollector`; every sampled frame is added to it under its video's index (with the segment statistics the
+    converter has already downloaded) and `tubes.json` is written beside `pred.json`. None: nothing else happens."""
     pred_pans_2ch = pred_pans_2ch[(labeled_fid // lambda_)::lambda_]            # only frames with GT annotations (:36)
     if color_generator is None:
         from panopticapi.utils import IdGenerator
@@ -633,6 +637,8 @@ def inference_panoptic_video(pred_pans_2ch, output_dir, categories, names, n_vid
         for j, (a, pan_dev) in enumerate(zip(ann, pans_dev)):
             i = v0 + j
             annotations.append(a)
+            if tubes is not None:
+                tubes.add(v0 // nframes_per_video, names[i] if names is not None else '%d' % i, twos_dev[j], stats=conv.frame_stats[j])
             if names is not None and on_device:
                 writer.submit(twos_dev[j], png_name(os.path.join(output_dir, 'pan_2ch'), names[i]))
                 writer.submit(pan_dev, png_name(os.path.join(output_dir, 'pan_pred'), names[i]))
@@ -647,6 +653,8 @@ def inference_panoptic_video(pred_pans_2ch, output_dir, categories, names, n_vid
     os.makedirs(output_dir, exist_ok=True)
     with open(os.path.join(output_dir, 'pred.json'), 'w') as f:
         json.dump(pred_json, f)
+    if tubes is not None:
+        tubes.write(os.path.join(output_dir, 'tubes.json'))
     if own:
         writer.close()
     return pan_all, pred_json
