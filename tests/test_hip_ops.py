@@ -1066,3 +1066,151 @@ def test_correlation_split_fp16_reports_the_fp16_range(dev):
     finally:
         nhwc.CORR_F16[0] = old
         nhwc.F16_FALLBACKS[0] = 0
+
+
+# ------------------------------------------------------------------------------------------------ detection ops: edges
+def _edge_rois(Hi, Wi, B, seed):
+    """RoIs wholly and partly outside the image, a one-pixel RoI, scales exactly on the level edges (112, 224, 448), random ones"""
+    fixed = [[-300, -300, -200, -200], [Wi + 50, Hi + 50, Wi + 150, Hi + 100], [-20, -10, 40, 30], [Wi - 30, Hi - 20, Wi + 40, Hi + 35],
+             [-50, 5, Wi + 60, 20], [17, 9, 17, 9], [10, 10, 121, 121], [5, 5, 228, 228], [0, 0, 447, 447], [3, 2, 113, 114], [0.4, 0.6, 6.2, 5.1]]
+    r = torch.cat([torch.tensor(fixed, dtype=torch.float32), _rand_rois(20, Hi, Wi, seed)[:, 1:]], 0)
+    b = (torch.arange(r.shape[0]) % B).float()
+    return torch.cat([b[:, None], r], 1)
+
+
+@pytest.mark.parametrize('nlevels,C,B,win,Hi,Wi', [(4, 4, 2, True, 256, 512), (4, 32, 2, False, 256, 512), (2, 8, 1, True, 8, 64), (1, 4, 2, False, 64, 96)],
+                         ids=['4lv_c4_b2_window', '4lv_c32_b2', '2lv_h1_window', '1lv_b2'])
+def test_roi_align_edges(dev, nlevels, C, B, win, Hi, Wi):
+    """vps_roi_align against the oracle's per-level roi_align: sample points outside the map (the zero branch), on the last row /
+    column (the clamp), batch index > 0, level maps that are channel windows of wider buffers (ld = C + 8, offset 4), 1 / 2 / 4
+    levels, C = 4, a level map with H = 1 (8 x 64 image at stride 8), and R = 0"""
+    from ctypes import c_float, c_int, c_void_p
+    lib = hip.load()
+    strides = [4, 8, 16, 32][:nlevels]
+    ld, off = (C + 8, 4) if win else (C, 0)
+    bufs = [_rand(B, Hi // s, Wi // s, ld, seed=s).to(dev).contiguous() for s in strides]
+    feats = [b[..., off:off + C].permute(0, 3, 1, 2).contiguous().cpu() for b in bufs]
+    if nlevels == 2:
+        assert feats[1].shape[2] == 1
+    rois = _edge_rois(Hi, Wi, B, seed=3)
+    R_, P = rois.shape[0], 7
+    ref = OF.roi_extract(feats, rois, P)
+    if nlevels == 4:
+        assert OF.map_roi_levels(rois, 4)[6:9].tolist() == [1, 2, 3]
+        assert float(ref[0].abs().max()) == 0.0 and float(ref[1].abs().max()) == 0.0          # wholly outside: zeros
+    ptrs = (c_void_p * nlevels)(*[b.data_ptr() + 4 * off for b in bufs]); lds = (c_int * nlevels)(*[ld] * nlevels)
+    Hs = (c_int * nlevels)(*[Hi // s for s in strides]); Ws = (c_int * nlevels)(*[Wi // s for s in strides])
+    sc = (c_float * nlevels)(*[1.0 / s for s in strides])
+    rd = rois.to(dev)
+    out = torch.full((R_ + 1, P, P, C), -7.0, device=dev)
+    hip.check(lib.vps_roi_align(ptrs, lds, Hs, Ws, sc, nlevels, 56.0, hip.ptr(rd), 0, C, P, 2, hip.ptr(out), hip.stream_ptr()), 'R = 0')
+    torch.cuda.synchronize()
+    assert bool((out == -7.0).all())
+    hip.check(lib.vps_roi_align(ptrs, lds, Hs, Ws, sc, nlevels, 56.0, hip.ptr(rd), R_, C, P, 2, hip.ptr(out), hip.stream_ptr()), 'vps_roi_align')
+    torch.cuda.synchronize()
+    assert bool((out[R_] == -7.0).all())
+    _cmp(out[:R_].permute(0, 3, 1, 2), ref, rtol=5e-5, atol=5e-5, what='roi align edges')
+
+
+def _run_nms(dev, boxes, counts, thr):
+    nb, nmax = boxes.shape[:2]
+    bd = boxes.to(dev); cd = torch.tensor(counts, dtype=torch.int32, device=dev)
+    cb = (nmax + 63) // 64
+    mask = torch.empty(nb * nmax * cb, dtype=torch.int64, device=dev)
+    keep = torch.full((nb, nmax), -7, dtype=torch.int32, device=dev)
+    nkeep = torch.full((nb,), -7, dtype=torch.int32, device=dev)
+    hip.check(hip.load().vps_nms_batched(hip.ptr(bd), nb, nmax, hip.ptr(cd), thr, hip.ptr(mask), hip.ptr(keep), hip.ptr(nkeep), hip.stream_ptr()), 'nms')
+    torch.cuda.synchronize()
+    return keep.cpu().numpy(), nkeep.cpu().numpy()
+
+
+@pytest.mark.parametrize('thr', [0.3, 0.7])
+def test_nms_batched_counts_around_the_block_size_and_duplicates(dev, thr):
+    """one call with 0, 1, 63, 64, 65 and 129 boxes (empty list, one box, around the 64-box block), duplicate boxes included;
+    the rows of `keep` past the kept count stay untouched"""
+    counts = [0, 1, 63, 64, 65, 129]
+    nmax = 129
+    boxes = torch.zeros(len(counts), nmax, 5)
+    refs = []
+    for i, n in enumerate(counts):
+        r = _rand_rois(max(n, 1), 120, 200, seed=40 + i)[:n, 1:]
+        if n > 4:
+            r[n // 2] = r[0]; r[n - 1] = r[n - 2]; r[3] = r[2]                      # duplicates: IoU exactly 1
+        sc = torch.sort(torch.rand(n, generator=torch.Generator().manual_seed(50 + i)), descending=True)[0]
+        boxes[i, :n] = torch.cat([r, sc[:, None]], 1)
+        refs.append(O._greedy_nms_sorted(r.numpy(), thr))
+    kp, nk = _run_nms(dev, boxes, counts, thr)
+    for i, n in enumerate(counts):
+        assert nk[i] == len(refs[i]) and np.array_equal(kp[i, :nk[i]], refs[i]), i
+        assert (kp[i, nk[i]:] == -7).all()
+        if n > 4:
+            assert n // 2 not in refs[i] and len(refs[i]) < n
+
+
+def test_nms_iou_exactly_at_the_threshold_is_kept(dev):
+    """integer boxes: 10 x 10 against its 10 x 5 half, IoU = 50 / 100 exactly = thr: strict '>', not suppressed; its duplicate is"""
+    d = torch.tensor([[[0, 0, 9, 9, .9], [0, 0, 9, 4, .8], [0, 0, 9, 9, .7], [20, 20, 29, 29, .6], [20, 25, 29, 29, .5]]], dtype=torch.float32)
+    assert O._greedy_nms_sorted(d[0, :, :4].numpy(), 0.5).tolist() == [0, 1, 3, 4]
+    kp, nk = _run_nms(dev, d, [5], 0.5)
+    assert nk[0] == 4 and kp[0, :4].tolist() == [0, 1, 3, 4]
+
+
+def test_nms_kept_boxes_of_block_0_suppress_column_blocks_past_32(dev):
+    """2200 boxes (35 column blocks) in dense overlapping chains: 64 columns of boxes 40 px apart, block b sits 0 / 3 / 6 / 9 px off
+    its column (IoU with the block-0 box 1 / 0.82 / 0.68 / 0.55 at thr 0.7: chains of kept and suppressed boxes), blocks 33 and 34
+    sit exactly ON the block-0 boxes - suppressed by a box kept in block 0 and by no other kept box: the second lap of the reduce
+    kernel's propagate loop (32 column blocks per lap)"""
+    n, thr = 2200, 0.7
+    i = np.arange(n)
+    b, lane = i // 64, i % 64
+    pat = np.where(lane % 2 == 0, np.array([0, 3, 6, 9])[b % 4], np.array([0, 6, 3, 9])[b % 4]).astype(np.float32)
+    pat[b >= 33] = 0
+    x1 = lane * 40.0 + pat
+    boxes = np.stack([x1, 0 * pat, x1 + 30, 0 * pat + 30, 1.0 - i / 4000.0], 1).astype(np.float32)
+    ref = O._greedy_nms_sorted(boxes[:, :4], thr)
+    assert ref.max() < 33 * 64 and len(ref) == 128 and set(range(64)) <= set(ref.tolist())
+    # only block-0 boxes stand against blocks 33 / 34: every other kept box is 6 px off its column (IoU 0.68 < thr)
+    assert (pat[ref[ref >= 64]] == 6).all()
+    kp, nk = _run_nms(dev, torch.from_numpy(boxes)[None], [n], thr)
+    assert nk[0] == len(ref) and np.array_equal(kp[0, :nk[0]], ref)
+
+
+@pytest.mark.parametrize('n', [1, 257])
+def test_delta2bbox_stds_ratio_clip_and_clamps(dev, n):
+    """target stds other than 1, dw / dh beyond the wh_ratio_clip in both signs, boxes clamped on each of the four sides"""
+    H, W = 256., 512.
+    stds = (0.1, 0.1, 0.2, 0.2)
+    anchors = _rand_rois(max(n, 8), 256, 512, seed=7)[:, 1:]
+    deltas = _rand(max(n, 8), 4, seed=8, scale=4.0)
+    deltas[0] = torch.tensor([0.5, -0.5, 25.0, -25.0])                              # 0.2 * 25 = 5 > log(1000 / 16) = 4.135
+    deltas[1, 2:] = torch.tensor([-30.0, 30.0])
+    anchors[:6] = torch.tensor([100., 100., 199., 179.]); deltas[2:6, 2:] = 0.5
+    deltas[2, 0] = -60.0; deltas[3, 0] = 60.0; deltas[4, 1] = -60.0; deltas[5, 1] = 60.0      # centres shifted six sizes: off each side
+    anchors, deltas = anchors[:n].contiguous(), deltas[:n].contiguous()
+    scores = torch.rand(n, generator=torch.Generator().manual_seed(9))
+    ref = torch.cat([OF.delta2bbox(anchors, deltas, (0, 0, 0, 0), stds, (256, 512)), scores[:, None]], 1)
+    if n > 8:
+        assert float(ref[2, 2]) == 0.0 and float(ref[3, 0]) == W - 1 and float(ref[4, 3]) == 0.0 and float(ref[5, 1]) == H - 1
+    ad, dd, sd_ = anchors.to(dev), deltas.to(dev), scores.to(dev)
+    out = torch.full((n + 1, 5), -7.0, device=dev)
+    hip.check(hip.load().vps_delta2bbox(hip.ptr(ad), hip.ptr(dd), hip.ptr(sd_), hip.ptr(out), n, *stds, H, W, hip.stream_ptr()), 'd2b')
+    torch.cuda.synchronize()
+    assert bool((out[n] == -7.0).all())
+    _cmp(out[:n], ref, rtol=1e-5, atol=1e-4, what='delta2bbox stds')
+
+
+def test_bbox_overlaps_strided_rows_disjoint_and_identical(dev):
+    """lda = 5 (detections with their score column), ldb = 4, as the tracker calls it; disjoint pairs give exactly 0, identical 1"""
+    m, n = 7, 41
+    a = torch.cat([_rand_rois(m, 256, 512, seed=11)[:, 1:], torch.full((m, 1), 1e6)], 1).contiguous()
+    b = _rand_rois(n, 256, 512, seed=12)[:, 1:].contiguous()
+    b[0] = a[0, :4]; b[5] = a[6, :4]
+    b[1] = torch.tensor([2000., 2000., 2100., 2050.]); b[2] = torch.tensor([-500., 10., -400., 60.])
+    ad, bd = a.to(dev), b.to(dev)
+    o = torch.full((m + 1, n), -7.0, device=dev)
+    hip.check(hip.load().vps_bbox_overlaps(hip.ptr(ad), 5, m, hip.ptr(bd), 4, n, hip.ptr(o), hip.stream_ptr()), 'iou')
+    torch.cuda.synchronize()
+    o = o.cpu()
+    assert bool((o[m] == -7.0).all())
+    assert float(o[0, 0]) == 1.0 and float(o[6, 5]) == 1.0 and bool((o[:m, 1] == 0).all()) and bool((o[:m, 2] == 0).all())
+    _cmp(o[:m], OF.bbox_overlaps(a[:, :4], b), rtol=1e-6, atol=1e-7, what='iou lda 5')
