@@ -447,6 +447,31 @@ int vps_jpeg_write_bound(int H, int W, int subsampling, int64_t* capacity);
 int vps_jpeg_write(const int16_t* coef, int H, int W, int subsampling, const uint16_t* qt, uint8_t* out, int64_t capacity,
                    int64_t* nbytes);
 
+/* JPEG output with the entropy coding on the DEVICE (opt-in: `entropy='device'`; csrc/jpeg_scan_ops.hip). The coefficients stay where
+ * vps_jpeg_encode_coef wrote them; the device writes the entropy-coded segment - the bytes vps_jpeg_write puts between the SOS header
+ * and EOI for the same coefficients, byte for byte - and the host copies that (about the size of the file) and puts the container
+ * round it.
+ * vps_jpeg_scan_bound (HOST arithmetic only): ws_bytes = the workspace of vps_jpeg_encode_scan, scan_bytes = the longest scan of that
+ * size = vps_jpeg_write_bound less the header and EOI. Either output may be NULL. Bit offsets on the device are 32-bit: a size whose
+ * worst-case scan has 2^32 bits or more (about 1.29 million blocks: 27 Mpixel at 4:4:4, 55 Mpixel at 4:2:0) returns an argument error
+ * here and in vps_jpeg_encode_scan.
+ * vps_jpeg_encode_scan (device; 5 launches on `stream`, no sync, no hidden allocation): coef = DEVICE int16 array of
+ * vps_jpeg_encode_coef, out = DEVICE buffer of `capacity` bytes (any capacity >= 0; may be NULL at 0), result = DEVICE int64 [2]
+ * (8-byte aligned), ws = DEVICE workspace (16-byte aligned, ws_bytes >= the bound; needs no initialisation). result[1] is the status:
+ *   0  out[0 : result[0]) is the scan
+ *   1  the scan has result[0] bytes and capacity is smaller: out holds its first `capacity` bytes; call again with result[0]
+ *   2  a DC difference of category > 11 or an AC coefficient of category > 10 (what vps_jpeg_write refuses): result[0] = 0, out untouched
+ * Nothing is stored at or beyond out + capacity or outside ws, whatever the coefficients are. The same input gives the same bytes on
+ * every call.
+ * vps_jpeg_wrap (HOST): header (SOI .. SOS, as vps_jpeg_write writes it) + scan[0 : scan_bytes) + EOI -> out, nbytes[0] = its size.
+ * The scan is copied, not parsed. A capacity below header + scan_bytes + 2, or a scan longer than vps_jpeg_scan_bound allows, is an
+ * argument error and nothing is stored. */
+int vps_jpeg_scan_bound(int H, int W, int subsampling, int64_t* ws_bytes, int64_t* scan_bytes);
+int vps_jpeg_encode_scan(const int16_t* coef, int H, int W, int subsampling, uint8_t* out, int64_t capacity, int64_t* result, void* ws,
+                         int64_t ws_bytes, void* stream);
+int vps_jpeg_wrap(const uint8_t* scan, int64_t scan_bytes, int H, int W, int subsampling, const uint16_t* qt, uint8_t* out,
+                  int64_t capacity, int64_t* nbytes);
+
 /* ref: models/anchor_heads/rpn_head.py:62-91 (sigmoid objectness, `scores.topk(nms_pre)`, gathers) + core/anchor/anchor_generator.py:55-72
  * (grid anchors) + core/bbox/transforms.py:34-68 (delta2bbox, means 0, clipped to the image) for ALL levels: one chip-wide scoring
  * launch + one select / sort / decode launch with one workgroup per level. cls[l] / reg[l]: NHWC maps [H_l][W_l][ld] of level l

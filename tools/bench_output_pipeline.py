@@ -22,6 +22,15 @@ Prints one JSON line and writes it to --out, stamped with `hip.csrc_sha16()`. Ne
                  thread count (1, 2, 4), on the same host
 Neither side had been measured before; the report states which one wins.
 
+`--leg overlay_entropy` measures the Huffman coding of those overlays on the device (`entropy='device'`) and adds the key
+`device_entropy` to profiles/overlay_output_pipeline.json; the other keys stay as they are.
+  device_ms      `vps_jpeg_encode_scan` (5 launches), the median of 30 with the slowest and fastest, timed with events, with its algorithmic bytes
+  host_ms        one frame on one thread: copy of the scan + `vps_jpeg_wrap` against copy of the coefficients + `vps_jpeg_write`
+  bytes          downloaded per frame in both modes
+  frames/s       `DeviceJpegWriter(entropy='device')` against `entropy='host'` - the writer as it was before the option existed - at 1, 2
+                 and 4 workers in the same process, the windows of the two modes alternating; the median of --repeats windows of --frames
+                 frames with the slowest and fastest
+
 `--leg flow` measures the optical-flow output (and writes profiles/flow_output_pipeline.json): a synthetic flow field (smooth motion
 plus noise) in FlowNet2's layout (NHWC, pixel stride 4), one file per frame.
   device_ms      `vps_flow_max_radius` and `vps_flow_colour`, each the median of 30, timed with events, with their algorithmic bytes over
@@ -198,6 +207,99 @@ def overlay_leg(args):
     rep['verdict'] = {str(n): ('device path %s: %.1f vs %.1f frames/s' % ('wins' if rep['device_writer'][str(n)]['frames_per_s'] > rep['host_numpy_pil'][str(n)]['frames_per_s'] else 'LOSES',
                                                                         rep['device_writer'][str(n)]['frames_per_s'], rep['host_numpy_pil'][str(n)]['frames_per_s'])) for n in (1, 2, 4)}
     rep['not_measured'] = 'a clip of the detector with --overlay against the same clip without it'
+    return rep
+
+
+def overlay_entropy_leg(args):
+    """`--leg overlay_entropy`: the Huffman coding of the overlay JPEGs on the device (`vps_jpeg_encode_scan`) against the host coder"""
+    import torch
+    from vps_amd import hip, synth
+    from vps_amd import postprocess as pp
+    assert torch.cuda.is_available(), 'the device encoder needs the MI355X'
+    dev = torch.device('cuda:0')
+    H, W, Q, A = args.height, args.width, 90, 128
+    colours = [painted(label_map(H, W, s), s) for s in range(4)]
+    frames = [synth.synth_frame(H, W, seed=s, shift=(2 * s, s), noise=2.0).astype(np.uint8) for s in range(4)]       # BGR
+    rgbs = [pp.render_overlay(torch.from_numpy(np.ascontiguousarray(f)).to(dev), torch.from_numpy(c).to(dev), A) for f, c in zip(frames, colours)]
+    rep = dict(size=[H, W], frames_per_window=args.frames, windows=args.repeats, quality=Q, subsampling='4:2:0', host_cpus=os.cpu_count(),
+               csrc_sha16=hip.csrc_sha16())
+    _, coef_bytes, _ = pp.jpeg_encode_bound(H, W)
+    wsb, scan_cap = pp.jpeg_scan_bound(H, W)
+    coefs = [pp.jpeg_encode_coef(r, Q, '4:2:0').clone() for r in rgbs]
+    out = torch.empty(coef_bytes // 4, dtype=torch.uint8, device=dev)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    result = torch.empty(2, dtype=torch.int64, device=dev)
+    for i in range(3):
+        pp.jpeg_encode_scan(coefs[i % 4], H, W, '4:2:0', out, ws, result)
+    torch.cuda.synchronize()
+    ms = []
+    for i in range(30):
+        e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
+        e0.record()
+        pp.jpeg_encode_scan(coefs[i % 4], H, W, '4:2:0', out, ws, result)
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    pp.jpeg_encode_scan(coefs[1], H, W, '4:2:0', out, ws, result)
+    n, status = (int(v) for v in result.cpu())
+    assert status == pp.JPEG_SCAN_OK, status
+    # bytes the algorithm needs: the coefficients read twice (size, pack), the unstuffed stream written once and read twice (count,
+    # stuff), the scan written, a 32-bit size per block written and read
+    alg = 2 * coef_bytes + 4 * n + 2 * 4 * (coef_bytes // 128)
+    med = float(np.median(ms))
+    rep['encode_scan'] = dict(device_ms_median_of_30=round(med, 4), device_ms_min=round(min(ms), 4), device_ms_max=round(max(ms), 4), launches=5,
+                              algorithmic_MB=round(alg / 1e6, 2), fraction_of_8TBps=round(alg / (med * 1e-3) / 8e12, 4), scan_bytes=n,
+                              workspace_MB=round(wsb / 1e6, 2), timed='events around the five launches, enqueue included')
+    # host side of one frame, one thread: copy of the scan + the container, against copy of the coefficients + vps_jpeg_write
+    pin_scan = torch.empty(out.numel(), dtype=torch.uint8).pin_memory()
+    pin_coef = torch.empty(coef_bytes // 2, dtype=torch.int16).pin_memory()
+    buf = np.empty(pp.jpeg_encode_bound(H, W)[2], dtype=np.uint8)
+    t = dict(scan_copy=[], wrap=[], coef_copy=[], jpeg_write=[])
+    for _ in range(10):
+        t0 = time.perf_counter()
+        pin_scan[:n].copy_(out[:n], non_blocking=True)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        data = pp.jpeg_wrap(pin_scan[:n], H, W, Q, '4:2:0', buf)
+        t2 = time.perf_counter()
+        pin_coef.copy_(coefs[1], non_blocking=True)
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        ref = pp.jpeg_write(pin_coef, H, W, Q, '4:2:0', buf)
+        t4 = time.perf_counter()
+        for k, v in zip(('scan_copy', 'wrap', 'coef_copy', 'jpeg_write'), (t1 - t0, t2 - t1, t3 - t2, t4 - t3)):
+            t[k].append(1e3 * v)
+    assert data == ref, 'the device scan differs from the host coder\'s'
+    rep['host_one_frame_ms_median_of_10'] = {k: round(float(np.median(v)), 3) for k, v in t.items()}
+    rep['bytes_downloaded_per_frame'] = dict(device_entropy=n + 16, host_entropy=coef_bytes, file_bytes=len(data))
+
+    def window(workers, entropy):
+        w = pp.DeviceJpegWriter(dev, workers=workers, slots=8, quality=Q, entropy=entropy)
+        with tempfile.TemporaryDirectory() as tmp:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for f in range(args.frames):
+                w.submit(rgbs[f % 4], os.path.join(tmp, '%04d.jpg' % f))
+            w.close()
+            dt = time.perf_counter() - t0
+        assert w.device_encoded == args.frames and w.fallback_encoded == 0
+        return args.frames / dt, w.bytes_downloaded / args.frames
+
+    rates = {(n_, e): [] for n_ in (1, 2, 4) for e in ('host', 'device')}
+    for n_, e in rates:                                              # warm-up: ring slots, pinned staging, copy streams
+        window(n_, e)
+    for _ in range(args.repeats):                                    # the two modes alternate, so a busy host hits both
+        for n_, e in rates:
+            rates[(n_, e)].append(window(n_, e)[0])
+    rep['writer_frames_per_s'] = {
+        str(n_): {e: dict(median=round(float(np.median(rates[(n_, e)])), 1), min=round(min(rates[(n_, e)]), 1), max=round(max(rates[(n_, e)]), 1))
+                  for e in ('host', 'device')} for n_ in (1, 2, 4)}
+    rep['verdict'] = {str(n_): "entropy='device' %s: %.1f vs %.1f frames/s" % (
+        'wins' if np.median(rates[(n_, 'device')]) > np.median(rates[(n_, 'host')]) else 'LOSES',
+        np.median(rates[(n_, 'device')]), np.median(rates[(n_, 'host')])) for n_ in (1, 2, 4)}
+    rep['comparison'] = "entropy='host' is the parent commit's DeviceJpegWriter, unchanged; same process, same box, windows alternating"
+    rep['not_measured'] = ('kernel times from a profiler trace (the event figure includes the enqueue of five launches); a detector clip with '
+                           '--overlay --jpeg-entropy device against the same clip without it; 4:4:4; other qualities')
     return rep
 
 
@@ -419,16 +521,26 @@ def tubes_leg(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--leg', default='png', choices=['png', 'overlay', 'flow', 'tubes'])
+    ap.add_argument('--leg', default='png', choices=['png', 'overlay', 'overlay_entropy', 'flow', 'tubes'])
     ap.add_argument('--frames', type=int, default=30)
-    ap.add_argument('--repeats', type=int, default=3, help='--leg flow / tubes: windows of --frames frames per writer figure (median and spread are reported)')
+    ap.add_argument('--repeats', type=int, default=3, help='--leg flow / tubes / overlay_entropy: windows of --frames frames per writer figure (median and spread are reported)')
     ap.add_argument('--height', type=int, default=1024)
     ap.add_argument('--width', type=int, default=2048)
     ap.add_argument('--out', default=None, help='default: profiles/<png|overlay|flow|tubes>_output_pipeline.json by --leg')
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(ROOT, 'profiles', {'png': 'png_output_pipeline.json', 'overlay': 'overlay_output_pipeline.json',
-                                                   'flow': 'flow_output_pipeline.json', 'tubes': 'tubes_output_pipeline.json'}[args.leg])
+                                                   'overlay_entropy': 'overlay_output_pipeline.json', 'flow': 'flow_output_pipeline.json',
+                                                   'tubes': 'tubes_output_pipeline.json'}[args.leg])
+    if args.leg == 'overlay_entropy':                                # a new key in the overlay report; the other keys stay as they are
+        rep = overlay_entropy_leg(args)
+        print(json.dumps(rep))
+        old = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        old['device_entropy'] = rep
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(json.dumps(old) + '\n')
+        return
     if args.leg in ('overlay', 'flow', 'tubes'):
         line = json.dumps({'overlay': overlay_leg, 'flow': flow_leg, 'tubes': tubes_leg}[args.leg](args))
         print(line)

@@ -54,6 +54,8 @@ def parse_args(argv=None):
     ap.add_argument('--overlay', default=None, metavar='DIR', help='write DIR/<name>.jpg for every frame: the panoptic result blended over the frame (off by default; '
                     'keeps every decoded frame on the device until the maps are unified, 6 MB per frame at 1024x2048)')
     ap.add_argument('--overlay-quality', type=int, default=90)
+    ap.add_argument('--jpeg-entropy', default='host', choices=['host', 'device'],
+                    help='where the JPEG files of --overlay and --flow are Huffman-coded; the files are the same (default host)')
     ap.add_argument('--overlay-alpha', type=int, default=128, help='weight of the colour map, 0..256')
     ap.add_argument('--flow', default=None, metavar='DIR', help='write DIR/<name>.<ext> for every frame: the FlowNet2 flow of the frame (off by default)')
     ap.add_argument('--flow-format', default='jpg', choices=['jpg', 'png', 'flo'], help='colour image (jpg, png) or the raw Middlebury field (flo)')
@@ -168,7 +170,7 @@ def run(args, tmp):
     if args.flow:
         from vps_amd.flowvis import FlowWriter, flow_name
         model.keep_flow = True
-        flow_writer = FlowWriter(dev, fmt=args.flow_format, max_rad=args.flow_max_rad)
+        flow_writer = FlowWriter(dev, fmt=args.flow_format, max_rad=args.flow_max_rad, entropy=args.jpeg_entropy)
     t0 = time.perf_counter()
     with torch.no_grad():
         for idx, im in enumerate(info):
@@ -226,8 +228,9 @@ def run(args, tmp):
         from vps_amd.postprocess import write_overlays
         order = sorted(range(len(res['all_names'])), key=lambda i: res['all_names'][i])                # the order of pred_pans_2ch
         ov = write_overlays(pred_pans_2ch, [res['all_frames'][i] for i in order], [res['all_names'][i] for i in order], args.overlay,
-                            ColorGenerator({c['id']: c for c in categories}), span, device=dev, quality=args.overlay_quality, alpha=args.overlay_alpha)
-        report['overlay'] = dict(dir=args.overlay, files=len(ov), quality=args.overlay_quality, alpha=args.overlay_alpha)
+                            ColorGenerator({c['id']: c for c in categories}), span, device=dev, quality=args.overlay_quality, alpha=args.overlay_alpha,
+                            entropy=args.jpeg_entropy)
+        report['overlay'] = dict(dir=args.overlay, files=len(ov), quality=args.overlay_quality, alpha=args.overlay_alpha, entropy=args.jpeg_entropy)
     report['run'] = dict(frames=len(info), seconds=round(dt, 3), frames_per_s=round(len(info) / dt, 2), decodes=feeder.decodes, output_dir=output_dir,
                          png_files=len(os.listdir(os.path.join(output_dir, 'pan_pred'))))
     truth_dir, gt_json = args.truth_dir, args.pan_gt_json

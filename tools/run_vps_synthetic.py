@@ -54,7 +54,7 @@ def uint8_frame(H, W, seed, shift):
     return synth.synth_frame(H, W, seed=seed, shift=shift, noise=2.0 if shift != (0, 0) else 0.0).astype(np.uint8)
 
 
-def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None):
+def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg_entropy='host'):
     """test_vpq.py:129-149 + single_gpu_test (:28-69) on `videos` synthetic clips -> pano_results with DEVICE maps.
     `flow` = (directory, format, max_rad): the FlowNet2 flow of EVERY frame as DIR/<name>.<format> (flowvis.FlowWriter)"""
     import vps_amd
@@ -77,7 +77,7 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None):
     if flow:
         from vps_amd.flowvis import FlowWriter, flow_name
         model.keep_flow = True
-        flow_writer = FlowWriter(dev, fmt=flow[1], max_rad=flow[2])
+        flow_writer = FlowWriter(dev, fmt=flow[1], max_rad=flow[2], entropy=jpeg_entropy)
     decoded = [[uint8_frame(H, W, seed=v, shift=(2 * f, f)) for f in range(nframes)] for v in range(videos)]   # "cv2.imread" results (BGR uint8)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -104,7 +104,7 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None):
     return res, time.perf_counter() - t0
 
 
-def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_png=False, overlay=None, tubes=False):
+def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_png=False, overlay=None, tubes=False, jpeg_entropy='host'):
     """test_vpq.py:178-198 with the device-side unifier / converter / asynchronous writer (`device_png`: the PNGs are filtered and
     deflated on the device too, postprocess.DevicePngWriter). `overlay` = (directory, quality, alpha): an overlay JPEG of EVERY frame,
     blended and transformed on the device (postprocess.write_overlays). `tubes`: tubes.json beside pred.json, the COCO run-length
@@ -134,7 +134,7 @@ def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_pn
         frames = {n: np.pad(f, ((0, two[n].shape[0] - f.shape[0]), (0, two[n].shape[1] - f.shape[1]), (0, 0)), mode='edge')
                   for n, f in zip(res['all_names'], res['all_frames'])}
         write_overlays(pred_pans_2ch, [frames[k] for k in keys], keys, overlay[0], ColorGenerator(cats), len(keys) // max(videos, 1), device=dev,
-                       quality=overlay[1], alpha=overlay[2])
+                       quality=overlay[1], alpha=overlay[2], entropy=jpeg_entropy)
     return names, pans, pj
 
 
@@ -170,6 +170,8 @@ def main():
     ap.add_argument('--overlay', default=None, metavar='DIR', help='write DIR/<name>.jpg for every frame: the panoptic result blended over the frame (off by default)')
     ap.add_argument('--overlay-quality', type=int, default=90)
     ap.add_argument('--overlay-alpha', type=int, default=128, help='weight of the colour map, 0..256')
+    ap.add_argument('--jpeg-entropy', default='host', choices=['host', 'device'],
+                    help='where the JPEG files of --overlay and --flow are Huffman-coded; the files are the same (default host)')
     ap.add_argument('--tubes', action='store_true', help='write pred/tubes.json: run-length encoded masks, boxes and areas of every tracked instance (off by default)')
     ap.add_argument('--flow', default=None, metavar='DIR', help='write DIR/<name>.<ext> for every frame: the FlowNet2 flow of the frame (off by default)')
     ap.add_argument('--flow-format', default='jpg', choices=['jpg', 'png', 'flo'], help='colour image (jpg, png) or the raw Middlebury field (flo)')
@@ -180,9 +182,10 @@ def main():
     overlay = (args.overlay, args.overlay_quality, args.overlay_alpha) if args.overlay else None
     nper = len(range(labeled_fid // lambda_, args.frames, lambda_))
     flow = (args.flow, args.flow_format, args.flow_max_rad) if args.flow else None
-    res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated, flow)
+    res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated, flow, args.jpeg_entropy)
     t0 = time.perf_counter()
-    names, pans, pj = postprocess(res, os.path.join(args.out, 'pred'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png, overlay, args.tubes)
+    names, pans, pj = postprocess(res, os.path.join(args.out, 'pred'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png, overlay, args.tubes,
+                                  args.jpeg_entropy)
     dpost = time.perf_counter() - t0
     pred = (pans, pj)
     gt = pred

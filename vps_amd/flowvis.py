@@ -136,13 +136,14 @@ class FlowWriter:
     """`DeviceJpegWriter`'s surface for flow fields: `submit(flow, name)` reads the flow on the CURRENT stream before it returns - the
     caller's buffer (a ring slot of the detector) may be overwritten right after - and leaves the rest to worker threads; it never
     synchronises the caller's stream and blocks only while every slot is busy.
-      fmt 'jpg'  `flow_colour` into a fresh image, handed to a `DeviceJpegWriter` of its own (which keeps the image alive)
+      fmt 'jpg'  `flow_colour` into a fresh image, handed to a `DeviceJpegWriter` of its own (which keeps the image alive); `entropy`
+                 ('host' or 'device') is that writer's: where the Huffman coding runs, the files are the same
       fmt 'png'  `flow_colour` into a fresh image, handed to a `DevicePngWriter` of its own
       fmt 'flo'  a stream-ordered copy of the two channels into one of `slots` pinned slots; a worker writes header + field
     max_rad (jpg / png): None = each frame's own maximum (the reference); a float or device float64 scalar = one normaliser for all
     frames. Counters: `submitted`; after `close()`, which joins and re-raises a worker's exception: `written`, `bytes_written`."""
 
-    def __init__(self, device='cuda', workers=2, slots=4, fmt='jpg', quality=90, max_rad=None):
+    def __init__(self, device='cuda', workers=2, slots=4, fmt='jpg', quality=90, max_rad=None, entropy='host'):
         if fmt not in FORMATS:
             raise ValueError('fmt is one of %s, got %r' % (FORMATS, fmt))
         self.device = torch.device(device)
@@ -150,7 +151,7 @@ class FlowWriter:
         self.max_rad = None if max_rad is None else max_rad_scalar(max_rad, self.device)
         self.images = self.pool = None
         if fmt == 'jpg':
-            self.images = pp.DeviceJpegWriter(self.device, workers=workers, slots=slots, quality=quality)
+            self.images = pp.DeviceJpegWriter(self.device, workers=workers, slots=slots, quality=quality, entropy=entropy)
         elif fmt == 'png':
             self.images = pp.DevicePngWriter(self.device, workers=workers, slots=slots)
         else:
@@ -215,12 +216,12 @@ def flow_name(save_folder, name, fmt='jpg'):
     return os.path.join(save_folder, os.path.splitext(os.path.basename(name))[0] + '.' + fmt)
 
 
-def write_flows(flows, names, out_dir, device='cuda', fmt='jpg', quality=90, max_rad=None, writer=None):
+def write_flows(flows, names, out_dir, device='cuda', fmt='jpg', quality=90, max_rad=None, writer=None, entropy='host'):
     """a file per frame, `out_dir/<name>.<fmt>`, through a `FlowWriter` (the caller's, or one made and closed here). `flows`: device
     flows in the order of `names`. Returns the file names."""
     assert len(flows) == len(names)
     own = writer is None
-    writer = FlowWriter(device, fmt=fmt, quality=quality, max_rad=max_rad) if own else writer
+    writer = FlowWriter(device, fmt=fmt, quality=quality, max_rad=max_rad, entropy=entropy) if own else writer
     out = []
     for flow, name in zip(flows, names):
         out.append(flow_name(out_dir, name, writer.fmt))

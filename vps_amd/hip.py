@@ -33,6 +33,7 @@ SYMBOLS = [
     'vps_png_inflate', 'vps_png_reconstruct_ws', 'vps_png_reconstruct', 'vps_png_reconstruct_block_rows',
     'vps_unify_tables_image', 'vps_segment_stats_ch', 'vps_segment_paint_ch', 'vps_sseg_confusion',
     'vps_overlay_render', 'vps_jpeg_quant_tables', 'vps_jpeg_encode_bound', 'vps_jpeg_encode_coef', 'vps_jpeg_write_bound', 'vps_jpeg_write',
+    'vps_jpeg_scan_bound', 'vps_jpeg_encode_scan', 'vps_jpeg_wrap',
     'vps_flow_max_radius', 'vps_flow_colour',
     'vps_rle_runs', 'vps_rle_runs_ws', 'vps_rle_band_rows', 'vps_rle_strings', 'vps_rle_strings_bound',
 ]
@@ -201,6 +202,9 @@ def load():
         h.vps_jpeg_encode_bound.argtypes = [c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int64)]
         h.vps_jpeg_write_bound.argtypes = [c_int, c_int, c_int, POINTER(c_int64)]
         h.vps_jpeg_write.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, POINTER(c_int64)]
+        h.vps_jpeg_scan_bound.restype = h.vps_jpeg_wrap.restype = c_int
+        h.vps_jpeg_scan_bound.argtypes = [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]
+        h.vps_jpeg_wrap.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, POINTER(c_int64)]
         h.vps_rle_strings.restype = c_int
         h.vps_rle_strings.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
         h.vps_rle_strings_bound.restype = c_int64
@@ -213,6 +217,7 @@ def load():
                                          c_void_p]
     lib.vps_overlay_render.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.vps_jpeg_encode_coef.argtypes = [c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.vps_jpeg_encode_scan.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]
     lib.vps_flow_max_radius.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.vps_flow_colour.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.vps_png_reconstruct_ws.argtypes = [c_int, c_int, c_int, POINTER(c_int64)]

@@ -380,7 +380,8 @@ class DevicePngWriter:
 # down-sampling, forward DCT and quantisation on the device (csrc/jpeg_enc_ops.hip), Huffman coding and the container on the host
 # without the interpreter lock (csrc/jpeg_enc_host.cpp): the JPEG input path of pipeline.py in the other direction. The files are the
 # ones libjpeg's default compressor (PIL's `save(format='JPEG', quality=q, subsampling=s)`) writes for the same pixels, scan byte for
-# scan byte.
+# scan byte. entropy='device' (opt-in) moves the Huffman coding to the device as well (csrc/jpeg_scan_ops.hip): the host copies the scan,
+# about the size of the file, and writes the container round it (`vps_jpeg_wrap`); the files are the same.
 # ------------------------------------------------------------------------------------------------------------------
 JPEG_SUBSAMPLING = {'4:2:0': 2, '4:4:4': 0, 2: 2, 0: 0}                         # the numbers are PIL's `subsampling=` values
 _jpeg_qt_cache = {}
@@ -481,24 +482,106 @@ def jpeg_write(coef, H, W, quality=90, subsampling='4:2:0', out=None):
     return out[:n.value].tobytes()
 
 
-def jpeg_encode(rgb, quality=90, subsampling='4:2:0'):
+JPEG_ENTROPY = ('host', 'device')
+JPEG_SCAN_OK, JPEG_SCAN_SHORT, JPEG_SCAN_RANGE = 0, 1, 2                        # result[1] of `vps_jpeg_encode_scan`
+
+
+def _entropy(e):
+    if e not in JPEG_ENTROPY:
+        raise ValueError("entropy is 'host' or 'device', got %r" % (e,))
+    return e
+
+
+def jpeg_scan_bound(H, W, subsampling='4:2:0'):
+    """(workspace bytes, worst-case scan bytes) of `vps_jpeg_encode_scan` for one image size (`vps_jpeg_scan_bound`)"""
+    import ctypes
+    wsb, cap = ctypes.c_int64(0), ctypes.c_int64(0)
+    hip.check(hip.load_host().vps_jpeg_scan_bound(H, W, _subsampling(subsampling), ctypes.byref(wsb), ctypes.byref(cap)), 'vps_jpeg_scan_bound')
+    return wsb.value, cap.value
+
+
+def jpeg_encode_scan(coef, H, W, subsampling='4:2:0', out=None, ws=None, result=None):
+    """Huffman-code device coefficients (as `jpeg_encode_coef` wrote them) on the device (`vps_jpeg_encode_scan`) on
+    the current stream, no sync. Returns (device uint8 buffer, device int64 [2] = bytes, status): with status JPEG_SCAN_OK the scan
+    between the SOS header and EOI is buffer[:bytes]; JPEG_SCAN_SHORT = `out` holds only its first `out.numel()` bytes of `bytes`;
+    JPEG_SCAN_RANGE = a coefficient the baseline tables have no code for. `out` / `ws` / `result`: caller-owned buffers (default:
+    fresh ones, `out` of the worst-case size)."""
+    assert torch.is_tensor(coef) and coef.is_cuda and coef.dtype == torch.int16 and coef.is_contiguous(), 'device int16 coefficients'
+    sub = _subsampling(subsampling)
+    assert coef.numel() * 2 >= jpeg_encode_bound(H, W, sub)[1]
+    if out is None or ws is None:
+        wsb, cap = jpeg_scan_bound(H, W, sub)
+        out = torch.empty(cap, dtype=torch.uint8, device=coef.device) if out is None else out
+        ws = torch.empty(wsb, dtype=torch.uint8, device=coef.device) if ws is None else ws
+    if result is None:
+        result = torch.empty(2, dtype=torch.int64, device=coef.device)
+    hip.check(hip.load().vps_jpeg_encode_scan(hip.ptr(coef), H, W, sub, hip.ptr(out), out.numel(), hip.ptr(result), hip.ptr(ws), ws.numel(),
+                                              hip.stream_ptr()), 'vps_jpeg_encode_scan')
+    return out, result
+
+
+def jpeg_wrap(scan, H, W, quality=90, subsampling='4:2:0', out=None):
+    """HOST scan bytes (uint8 numpy, or a CPU tensor such as pinned staging) -> the bytes of the baseline JFIF file: the header
+    `jpeg_write` writes, the scan, EOI (`vps_jpeg_wrap`, no interpreter lock). `out`: reusable uint8 numpy buffer, grown when too small."""
+    import ctypes
+    if torch.is_tensor(scan):
+        assert not scan.is_cuda and scan.dtype == torch.uint8 and scan.is_contiguous()
+        sptr, n = ctypes.c_void_p(scan.data_ptr()), scan.numel()
+    else:
+        scan = np.ascontiguousarray(scan, dtype=np.uint8)
+        sptr, n = scan.ctypes.data_as(ctypes.c_void_p), scan.size
+    qt = jpeg_quant_tables(quality)
+    if out is None or out.size < n + 1024:
+        out = np.empty(n + 1024, dtype=np.uint8)                                 # the header and EOI are 625 bytes
+    nb = ctypes.c_int64(0)
+    hip.check(hip.load_host().vps_jpeg_wrap(sptr, n, H, W, _subsampling(subsampling), qt.ctypes.data_as(ctypes.c_void_p),
+                                            out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(nb)), 'vps_jpeg_wrap')
+    return out[:nb.value].tobytes()
+
+
+def jpeg_encode(rgb, quality=90, subsampling='4:2:0', entropy='host'):
     """device RGB uint8 [H,W,3] -> bytes of a baseline JPEG, the file PIL's `save(format='JPEG', quality=quality, subsampling=subsampling)`
-    writes from the SOS marker on. Synchronises (one download of the coefficients); `DeviceJpegWriter` is the asynchronous form."""
+    writes from the SOS marker on. Synchronises; `DeviceJpegWriter` is the asynchronous form. entropy 'host': one download of the
+    coefficients, `vps_jpeg_write`. 'device': `jpeg_encode_scan` into a buffer of an eighth of the coefficients' size - repeated once
+    with the exact size when the scan is longer - and one download of the scan; the same bytes."""
     t, H, W, _, _ = _png_view(rgb)
     coef = jpeg_encode_coef(t, quality, subsampling)
-    return jpeg_write(coef.cpu().numpy(), H, W, quality, subsampling)
+    if _entropy(entropy) == 'host':
+        return jpeg_write(coef.cpu().numpy(), H, W, quality, subsampling)
+    ws = torch.empty(jpeg_scan_bound(H, W, subsampling)[0], dtype=torch.uint8, device=t.device)
+    out = torch.empty(max(4096, coef.numel() // 4), dtype=torch.uint8, device=t.device)
+    out, result = jpeg_encode_scan(coef, H, W, subsampling, out, ws)
+    n, status = (int(v) for v in result.cpu())
+    if status == JPEG_SCAN_SHORT:
+        out, result = jpeg_encode_scan(coef, H, W, subsampling, torch.empty(n, dtype=torch.uint8, device=t.device), ws)
+        n, status = (int(v) for v in result.cpu())
+    if status != JPEG_SCAN_OK:
+        raise hip.VpsHipError('vps_jpeg_encode_scan: status %d (a coefficient outside the range of 8-bit baseline data)' % status)
+    return jpeg_wrap(out[:n].cpu().numpy(), H, W, quality, subsampling)
 
 
 class _JpegSlot:
     def __init__(self, device):
         self.device = device
         self.coef = self.host = self.image = None
+        self.scan = self.ws = self.scan_host = None      # entropy 'device' only
         self.event = torch.cuda.Event()
 
-    def fit(self, nelem):
+    def fit(self, nelem, pinned=True):
         if self.coef is None or self.coef.numel() < nelem:
             self.coef = torch.empty(nelem, dtype=torch.int16, device=self.device)
-            self.host = torch.empty(nelem, dtype=torch.int16).pin_memory()
+            self.host = torch.empty(nelem, dtype=torch.int16).pin_memory() if pinned else None
+
+    def fit_scan(self, cap, wsb):
+        """scan buffer + pinned staging of `cap` bytes, workspace, result (device and pinned)"""
+        if self.scan is None:
+            self.result = torch.empty(2, dtype=torch.int64, device=self.device)
+            self.result_host = torch.empty(2, dtype=torch.int64).pin_memory()
+        if self.scan is None or self.scan.numel() < cap:
+            self.scan = torch.empty(cap, dtype=torch.uint8, device=self.device)
+            self.scan_host = torch.empty(cap, dtype=torch.uint8).pin_memory()
+        if self.ws is None or self.ws.numel() < wsb:
+            self.ws = torch.empty(wsb, dtype=torch.uint8, device=self.device)
 
 
 class DeviceJpegWriter:
@@ -507,15 +590,21 @@ class DeviceJpegWriter:
     an event and returns - it never synchronises the caller's stream and blocks only while every slot is busy. A worker thread waits for
     the event, downloads the coefficients on its own copy stream, runs `vps_jpeg_write` (no interpreter lock) into a buffer it keeps, and
     writes the file. Host arrays are uploaded first: there is no host encoder here. Counters: `submitted`, `device_encoded`,
-    `bytes_written`. `close()` joins and re-raises a worker's exception."""
+    `bytes_written`, `bytes_downloaded`. `close()` joins and re-raises a worker's exception.
+    entropy='device' (default 'host', the above): `submit` also enqueues `jpeg_encode_scan` and the copy of its 16-byte result; the slot
+    holds a scan buffer of `scan_capacity` bytes (default: a quarter of the coefficients' bytes, 2 bits per coefficient), the workspace
+    and pinned staging for the scan in place of the staging for the coefficients. The worker copies exactly the scan's bytes and puts
+    the container round them (`vps_jpeg_wrap`): the same file. A scan that does not fit the slot, or a coefficient out of range, sends
+    that frame through the host coder as above (unpinned download) and is counted in `fallback_encoded`; the others in `scan_encoded`."""
     accepts_device = True
 
-    def __init__(self, device='cuda', workers=2, slots=4, quality=90, subsampling='4:2:0'):
+    def __init__(self, device='cuda', workers=2, slots=4, quality=90, subsampling='4:2:0', entropy='host', scan_capacity=None):
         import queue
         import threading
         from concurrent.futures import ThreadPoolExecutor
         self.device = torch.device(device)
         self.quality, self.subsampling = int(quality), _subsampling(subsampling)
+        self.entropy, self.scan_capacity = _entropy(entropy), scan_capacity
         jpeg_quant_tables(self.quality)                  # a bad quality raises here, not in a worker
         self.pool = ThreadPoolExecutor(max_workers=workers)
         self.futures = []
@@ -526,21 +615,47 @@ class DeviceJpegWriter:
         self.lock = threading.Lock()
         self.submitted = 0           # images handed to submit()
         self.device_encoded = 0      # files written from device coefficients
+        self.scan_encoded = 0        # ... of them: files whose scan came from vps_jpeg_encode_scan
+        self.fallback_encoded = 0    # entropy 'device' frames the host coder wrote (scan slot too small, coefficient out of range)
         self.bytes_written = 0
+        self.bytes_downloaded = 0    # device -> host, coefficients or scan + result
+
+    def _host_coded(self, coef_host, H, W):
+        cap = jpeg_encode_bound(H, W, self.subsampling)[2]
+        if self.local.out is None or self.local.out.size < cap:
+            self.local.out = np.empty(cap, dtype=np.uint8)    # pages of the worst case that no file reaches are never touched
+        return jpeg_write(coef_host, H, W, self.quality, self.subsampling, self.local.out)
 
     def _finish(self, slot, name, H, W, nelem):
+        scanned = False
         try:
             slot.event.synchronize()                     # the worker waits, not the caller
             if not hasattr(self.local, 'stream'):
                 self.local.stream = torch.cuda.Stream(self.device)
                 self.local.out = None
-            with torch.cuda.stream(self.local.stream):
-                slot.host[:nelem].copy_(slot.coef[:nelem], non_blocking=True)
-                self.local.stream.synchronize()
-            cap = jpeg_encode_bound(H, W, self.subsampling)[2]
-            if self.local.out is None or self.local.out.size < cap:
-                self.local.out = np.empty(cap, dtype=np.uint8)    # pages of the worst case that no file reaches are never touched
-            data = jpeg_write(slot.host, H, W, self.quality, self.subsampling, self.local.out)
+            if self.entropy == 'device':
+                n, status = int(slot.result_host[0]), int(slot.result_host[1])
+                scanned = status == JPEG_SCAN_OK
+                down = 16
+            if scanned:
+                with torch.cuda.stream(self.local.stream):
+                    slot.scan_host[:n].copy_(slot.scan[:n], non_blocking=True)
+                    self.local.stream.synchronize()
+                if self.local.out is None or self.local.out.size < n + 1024:
+                    self.local.out = np.empty(max(1 << 16, 1 << (n + 1024).bit_length()), dtype=np.uint8)
+                data = jpeg_wrap(slot.scan_host[:n], H, W, self.quality, self.subsampling, self.local.out)
+                down += n
+            elif self.entropy == 'device':
+                with torch.cuda.stream(self.local.stream):
+                    coef_host = slot.coef[:nelem].cpu()
+                data = self._host_coded(coef_host, H, W)
+                down += 2 * nelem
+            else:
+                with torch.cuda.stream(self.local.stream):
+                    slot.host[:nelem].copy_(slot.coef[:nelem], non_blocking=True)
+                    self.local.stream.synchronize()
+                data = self._host_coded(slot.host, H, W)
+                down = 2 * nelem
         finally:
             slot.image = None
             self.free.put(slot)
@@ -550,6 +665,10 @@ class DeviceJpegWriter:
         with self.lock:
             self.device_encoded += 1
             self.bytes_written += len(data)
+            self.bytes_downloaded += down
+            if self.entropy == 'device':
+                self.scan_encoded += scanned
+                self.fallback_encoded += not scanned
         return name
 
     def submit(self, image, name):
@@ -560,9 +679,14 @@ class DeviceJpegWriter:
         nelem = jpeg_encode_bound(H, W, self.subsampling)[1] // 2
         slot = self.free.get()                           # blocks only when every slot is in flight
         try:
-            slot.fit(nelem)
+            slot.fit(nelem, pinned=self.entropy == 'host')
             slot.image = t                               # alive until the worker is done with it
             jpeg_encode_coef(t, self.quality, self.subsampling, slot.coef)
+            if self.entropy == 'device':
+                cap = nelem // 2 if self.scan_capacity is None else int(self.scan_capacity)
+                slot.fit_scan(max(cap, 1), jpeg_scan_bound(H, W, self.subsampling)[0])
+                jpeg_encode_scan(slot.coef[:nelem], H, W, self.subsampling, slot.scan, slot.ws, slot.result)
+                slot.result_host.copy_(slot.result, non_blocking=True)
             slot.event.record()
         except BaseException:
             slot.image = None
@@ -586,14 +710,15 @@ def overlay_name(save_folder, name):
 
 
 def write_overlays(pred_pans_2ch, frames, names, out_dir, color_generator, nframes_per_video, device='cuda', alpha=128, quality=90,
-                   writer=None):
+                   writer=None, entropy='host'):
     """an overlay JPEG of EVERY frame: `pred_pans_2ch` (the unified 3-channel maps, host or device) are painted per video by
     `TrackConverter.convert_device` (a track keeps its colour through its video), blended over `frames` (BGR uint8 [H,W,3], host or
     device, same order) by `render_overlay` and written as `out_dir/<name>.jpg` through a `DeviceJpegWriter` (the caller's, or one made
-    and closed here). `color_generator`: its own instance - the colours of pred.json are not touched. Returns the file names."""
+    and closed here, with `entropy` 'host' or 'device'). `color_generator`: its own instance - the colours of pred.json are not touched.
+    Returns the file names."""
     assert len(pred_pans_2ch) == len(frames) == len(names)
     own = writer is None
-    writer = DeviceJpegWriter(device, quality=quality) if own else writer
+    writer = DeviceJpegWriter(device, quality=quality, entropy=entropy) if own else writer
     conv = TrackConverter(device)
     out = []
     for v0 in range(0, len(pred_pans_2ch), nframes_per_video):
