@@ -472,6 +472,61 @@ int vps_jpeg_encode_scan(const int16_t* coef, int H, int W, int subsampling, uin
 int vps_jpeg_wrap(const uint8_t* scan, int64_t scan_bytes, int H, int W, int subsampling, const uint16_t* qt, uint8_t* out,
                   int64_t capacity, int64_t* nbytes);
 
+/* Y4M video in and out (vps_amd/y4m.py; csrc/y4m_host.cpp + csrc/yuv_ops.hip): the uncompressed YUV4MPEG2 container, 8-bit planar
+ * frames. The host only parses the two kinds of header line; chroma resampling and the colour matrix run on the device.
+ * A stream is `YUV4MPEG2 W.. H.. [F..:..] [I.] [A..:..] [C..] [X..]\n` followed by frames of `FRAME[ params]\n` + Y, Cb, Cr planes.
+ * vps_y4m_info (HOST; untrusted bytes: never reads past nbytes, allocates nothing): parses the stream header. W and H are required,
+ * positive and W*H < 2^31; F and A are reported (0:0 when absent); I may be p or ? (t, b, m refused); C is 420jpeg, 420mpeg2, 420
+ * (= 420jpeg, also when absent), 422, 444 or mono; XCOLORRANGE=FULL|LIMITED is honoured (absent: limited), other X tags are ignored.
+ * The line is at most 256 bytes with its newline. Refusals, each -1000-x: 1 null / negative argument, 2 not the magic, 3 no newline
+ * within nbytes / 256 bytes, 4 malformed number or ratio, 5 W or H missing, 6 size not positive, 7 size too large, 8 interlaced,
+ * 9 420paldv, 10 more than 8 bits per sample, 11 444alpha, 12 unknown C, 13 unknown XCOLORRANGE, 14 unknown I.
+ * vps_y4m_frame_header (HOST): buf starts a frame: `FRAME`, then a newline or a blank and parameters (skipped) up to the newline,
+ * at most 80 bytes in all; len[0] = bytes of the line. 20 = not a FRAME line, 21 = no newline within nbytes / 80 bytes.
+ * vps_y4m_write_header (HOST): the header line of `info` (W, H, F unless 0:0, Ip when interlace is 1, A, C, XCOLORRANGE), which
+ * vps_y4m_info parses back to the same struct; len[0] = its bytes. 30 = a field out of range, 31 = capacity too small (nothing stored). */
+enum { VPS_Y4M_420JPEG = 0, VPS_Y4M_420MPEG2 = 1, VPS_Y4M_422 = 2, VPS_Y4M_444 = 3, VPS_Y4M_MONO = 4 };
+enum { VPS_YUV_LIMITED = 0, VPS_YUV_FULL = 1 };
+enum { VPS_YUV_BT601 = 0, VPS_YUV_BT709 = 1 };
+typedef struct vps_y4m_desc {
+    int32_t W, H;                 /* luma size */
+    int32_t CW, CH;               /* chroma plane size, rounded up for odd W / H; 0, 0 for mono */
+    int32_t sampling;             /* VPS_Y4M_* : sub-sampling and chroma siting */
+    int32_t range;                /* VPS_YUV_LIMITED / VPS_YUV_FULL */
+    int32_t fps_num, fps_den;     /* F tag; 0:0 = absent */
+    int32_t aspect_num, aspect_den;   /* A tag; 0:0 = unknown or absent */
+    int32_t interlace;            /* 1 = Ip, 0 = I? or absent */
+    int32_t header_bytes;         /* the header line with its newline */
+    int64_t frame_bytes;          /* payload of one frame: W*H + 2*CW*CH */
+} vps_y4m_desc;
+int vps_y4m_info(const uint8_t* buf, int64_t nbytes, vps_y4m_desc* info);
+int vps_y4m_frame_header(const uint8_t* buf, int64_t nbytes, int32_t* len);
+int vps_y4m_write_header(const vps_y4m_desc* info, uint8_t* out, int64_t capacity, int32_t* len);
+
+/* Colour conversion and chroma resampling of such frames (csrc/yuv_ops.hip; device, launch on `stream`, no sync, no allocation).
+ * Integer arithmetic throughout (csrc/yuv_tables.h): every coefficient is round(65536 * c) with c from (Kr, Kb) = (0.299, 0.114) for
+ * VPS_YUV_BT601, (0.2126, 0.0722) for VPS_YUV_BT709 and the range's offsets / scales (16 / 219 / 224 limited, 0 / 255 / 255 full);
+ * every output is (sum + 32768) >> 16, clamped to 0..255 (decode, full-range encode) or 16..235 / 16..240 (limited-range encode).
+ * tests/y4m_restate.py is the NumPy twin; results are equal byte for byte.
+ * vps_yuv_to_bgr: frame = DEVICE planar frame (4-byte aligned; Y [H][W], then Cb, Cr [CH][CW] as vps_y4m_info sizes them for
+ * `sampling`, tightly packed, frame_bytes >= that) -> out = BGR uint8 [H][W][3] dense, out_capacity >= 3*H*W bytes. Chroma is
+ * up-sampled bilinearly at the declared siting with weights of denominator 4 per axis, (sum wy*wx*s + 8) >> 4 over the 2x2
+ * neighbourhood with replicated borders: a centre-sited axis (420jpeg both, 420mpeg2 vertical) weights the nearer / farther sample
+ * 3, 1; a co-sited axis (420mpeg2 and 422 horizontal) 4, 0 on even and 2, 2 on odd positions; mono uses Cb = Cr = 128.
+ * vps_bgr_to_yuv: bgr = DEVICE uint8 [H][W][3] with row_stride >= 3*W bytes between rows, bytes B, G, R (rgb_order 0: a decoded
+ * frame) or R, G, B (rgb_order 1: what vps_overlay_render writes) -> out = planar frame of `sampling`
+ * (VPS_Y4M_444, VPS_Y4M_420JPEG or VPS_Y4M_420MPEG2), out_capacity >= its frame_bytes. Chroma is converted per pixel, then
+ * reduced: 420jpeg by a 2x2 box, (sum + 2) >> 2; 420mpeg2 by (1, 2, 1) horizontally centred on the even column times the row pair,
+ * (sum + 4) >> 3; source indices are clamped to the image. One launch, no intermediate plane.
+ * Refusals: 1 null pointer or size not positive / W*H >= 2^31, 2 sampling, 3 range or matrix, 4 capacity / frame_bytes / stride too
+ * small, 5 frame not 4-byte aligned. Nothing is launched and nothing is written on a refusal. */
+int vps_yuv_to_bgr(const uint8_t* frame, int64_t frame_bytes, int H, int W, int sampling, int range, int matrix, uint8_t* out,
+                   int64_t out_capacity, void* stream);
+int vps_bgr_to_yuv(const uint8_t* bgr, int H, int W, int64_t row_stride, int rgb_order, int sampling, int range, int matrix,
+                   uint8_t* out, int64_t out_capacity, void* stream);
+/* the pixels one workgroup of each kernel covers, rows then columns (HOST; constants of the build, for tests that cross a tile) */
+int vps_yuv_tile(int32_t* to_bgr_rows_cols, int32_t* to_yuv_rows_cols);
+
 /* ref: models/anchor_heads/rpn_head.py:62-91 (sigmoid objectness, `scores.topk(nms_pre)`, gathers) + core/anchor/anchor_generator.py:55-72
  * (grid anchors) + core/bbox/transforms.py:34-68 (delta2bbox, means 0, clipped to the image) for ALL levels: one chip-wide scoring
  * launch + one select / sort / decode launch with one workgroup per level. cls[l] / reg[l]: NHWC maps [H_l][W_l][ld] of level l

@@ -392,6 +392,133 @@ def png_device_mode(args):
     print(line)
 
 
+def merge_y4m_profile(path, key, rep):
+    """profiles/y4m_pipeline.json has one key per tool ('input': this file's --y4m, 'output': bench_output_pipeline.py --leg y4m)"""
+    old = json.load(open(path)) if os.path.exists(path) else {}
+    old = old if set(old) <= {'input', 'output'} else {}
+    old[key] = rep
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, 'w') as f:
+        json.dump(old, f, indent=1)
+        f.write('\n')
+
+
+def time_kernel(fn, pool, batch=20, reps=30):
+    """device ms per call: `reps` samples, each `batch` back-to-back launches between two events divided by `batch` (one launch alone
+    is at the scale of the launch itself) -> median, min, max. `pool`: how many different inputs / outputs the calls cycle through."""
+    import torch
+    for i in range(batch):
+        fn(i % pool)
+    torch.cuda.synchronize()
+    ms, k = [], 0
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(batch):
+            fn(k % pool)
+            k += 1
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1) / batch)
+    return dict(ms_median=round(float(np.median(ms)), 5), ms_min=round(min(ms), 5), ms_max=round(max(ms), 5), samples=reps, launches_per_sample=batch)
+
+
+def y4m_mode(args):
+    """--y4m: the Y4M input path at 420jpeg. `vps_yuv_to_bgr` by events, and the feeder drained by an idle consumer from a .y4m file
+    against the same frames as PNG files with png='host', same process, alternating windows. Writes the 'input' key of --out."""
+    import torch
+    from PIL import Image
+    from vps_amd import hip, synth, y4m
+    from vps_amd.pipeline import ClipFeeder, DeviceImagePrep
+    assert torch.cuda.is_available(), 'the conversion runs on the device'
+    dev = torch.device('cuda:0')
+    H, W = args.height, args.width
+    workers = [w for w in args.workers if w <= 4] or [1, 2, 4]
+    tmp = tempfile.mkdtemp(prefix='vps_input_')
+    frames = [np.ascontiguousarray(synth.synth_frame(H, W, seed=t % 4, shift=(2 * (t % 8), t % 8), noise=2.0).astype(np.uint8)) for t in range(args.frames)]
+    frames = [np.pad(f, ((0, H - f.shape[0]), (0, W - f.shape[1]), (0, 0)), mode='edge') for f in frames]
+    files = []
+    for t, fr in enumerate(frames):
+        fn = os.path.join(tmp, 'f%04d_leftImg8bit.png' % t)
+        Image.fromarray(np.ascontiguousarray(fr[:, :, ::-1])).save(fn, compress_level=6)
+        files.append(fn)
+    nmax = max(workers)
+    total = 2 * nmax + 1 + args.feeder_frames + 2 * nmax + 2
+    path = os.path.join(tmp, 'clip.y4m')
+    wr = y4m.Y4mWriter(path, W, H, sampling='420jpeg', device=dev)
+    dframes = [torch.from_numpy(f).to(dev) for f in frames]
+    for k in range(total):                                                    # the same frames, in the order the PNG clip cycles them
+        wr.submit(dframes[k % len(dframes)])
+    wr.close()
+    reader = y4m.Y4mReader(path)
+    info = reader.info
+    out = dict(mode='y4m-input', size=[H, W], sampling='420jpeg', range='limited', matrix='bt601', host_cpus=os.cpu_count(), csrc_sha16=hip.csrc_sha16(),
+               y4m_MB_per_frame=round(info.frame_bytes / 1e6, 2), png_MB_per_frame=round(sum(os.path.getsize(f) for f in files) / 1e6 / len(files), 2),
+               bgr_MB_per_frame=round(3 * H * W / 1e6, 2), clip_frames=len(reader),
+               files='written just before they are read: both the .y4m file and the PNG files come from the page cache, not from the disk')
+    # ---- the kernel: a few inputs that stay in the 256 MiB Infinity Cache, and a pool of inputs + outputs beyond it ----------------------------
+    rs = np.random.RandomState(0)
+    moved = info.frame_bytes + 3 * H * W
+    npool = int(2 * (256 << 20) // moved) + 2
+    src = [torch.from_numpy(rs.randint(0, 256, info.frame_bytes, dtype=np.uint8)).to(dev) for _ in range(4)]
+    src += [src[k % 4].clone() for k in range(4, npool)]
+    dst = [torch.empty(H, W, 3, dtype=torch.uint8, device=dev) for _ in range(npool)]
+    res = time_kernel(lambda i: y4m.yuv_to_bgr(src[i], info, 'bt601', dst[i]), 4)
+    out['vps_yuv_to_bgr_cache_resident'] = dict(res, inputs_cycled=4, working_set_MB=round(4 * moved / 1e6, 1), GBps_at_median=round(moved / res['ms_median'] / 1e6, 1))
+    res = time_kernel(lambda i: y4m.yuv_to_bgr(src[i], info, 'bt601', dst[i]), npool)
+    out['vps_yuv_to_bgr_beyond_cache'] = dict(res, inputs_cycled=npool, working_set_MB=round(npool * moved / 1e6, 1), GBps_at_median=round(moved / res['ms_median'] / 1e6, 1))
+    out['kernel_bytes_moved'] = moved
+    del src, dst
+    # ---- the feeder ------------------------------------------------------------------------------------------------------------------------------
+    prep = DeviceImagePrep(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True, size_divisor=32,
+                           img_scale=(max(H, W), min(H, W)), device=dev)
+
+    def window(mode, nw):
+        # steady state, as in --png-device: the clock starts after the first read-ahead window + 1 frames and stops with a full window to come
+        warm, timed = 2 * nw + 1, args.feeder_frames
+        clip = [files[k % len(files)] for k in range(warm + timed + 2 * nw + 2)]
+        fd = ClipFeeder(clip if mode == 'png' else reader, prep, workers=nw, png='host')
+        for k in range(warm):
+            fd(k)
+        torch.cuda.synchronize()
+        w0, u0 = fd.stats['wait_for_decode_s'], fd.stats['upload_prep_s']
+        t0 = time.perf_counter()
+        for k in range(warm, warm + timed):
+            fd(k)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        fd.close()
+        assert fd.fallback_decodes == 0 and fd.out_of_window == 0 and fd.native_y4m == (warm + timed if mode == 'y4m' else 0)
+        return timed / dt, fd.stats['wait_for_decode_s'] - w0, fd.stats['upload_prep_s'] - u0
+
+    runs = {(nw, m): [] for nw in workers for m in ('png', 'y4m')}
+    for key in runs:                                                          # warm-up: pinned rings, the library's buffers
+        window(key[1], key[0])
+    for _ in range(args.repeats):                                             # the two sources alternate, so a busy host hits both
+        for key in runs:
+            runs[key].append(window(key[1], key[0]))
+    out['feeder_frames_per_s'] = {
+        str(nw): {m: dict(median=round(float(np.median([r[0] for r in runs[(nw, m)]])), 1), min=round(min(r[0] for r in runs[(nw, m)]), 1),
+                          max=round(max(r[0] for r in runs[(nw, m)]), 1),
+                          wait_for_decode_s_median=round(float(np.median([r[1] for r in runs[(nw, m)]])), 4),
+                          upload_prep_s_median=round(float(np.median([r[2] for r in runs[(nw, m)]])), 4)) for m in ('png', 'y4m')} for nw in workers}
+    out['feeder_timed_frames'], out['feeder_windows'] = args.feeder_frames, args.repeats
+    out['feeder_note'] = ('consumer = fd(t) in a loop on an otherwise idle main thread (no detector beside it); steady state: the clock starts after '
+                          '2 x workers + 1 frames and stops with a full read-ahead window still to come; png = ClipFeeder(png=host) on the same frames')
+    y1 = out['feeder_frames_per_s'][str(min(workers))]['y4m']['median']
+    p4 = out['feeder_frames_per_s'][str(max(workers))]['png']['median']
+    out['expectation'] = 'one Y4M worker (%.1f frames/s) %s the %d-worker PNG rate (%.1f frames/s)' % (
+        y1, 'exceeds' if y1 > p4 else 'does NOT exceed', max(workers), p4)
+    out['not_measured'] = 'a detector clip fed from Y4M against the same clip from PNG; a .y4m file read from a cold disk; other samplings'
+    reader.close()
+    for f in files + [path]:
+        os.remove(f)
+    os.rmdir(tmp)
+    if args.out:
+        merge_y4m_profile(args.out, 'input', out)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=48)
@@ -408,6 +535,9 @@ def main():
     ap.add_argument('--png-workers', type=int, default=6, help='--clip: decode threads, as bench.py --png-workers')
     ap.add_argument('--prec', default='f16x3', choices=['f32', 'bf16x6', 'f16x3'], help='--clip: arithmetic of the detector, as bench.py --prec')
     ap.add_argument('--parent-lib', default=None, help='png-device mode: a library with another build of vps_png_decode_bgr8, timed beside this one')
+    ap.add_argument('--y4m', action='store_true', help="the Y4M input path: vps_yuv_to_bgr by events, the feeder from a .y4m file against the same frames as "
+                    "PNG files (png='host') at the --workers up to 4, alternating windows; --out defaults to profiles/y4m_pipeline.json (key 'input')")
+    ap.add_argument('--repeats', type=int, default=3, help='--y4m: windows per feeder figure (median and spread are reported)')
     ap.add_argument('--node', type=int, default=0, help='node mode: this many rank processes decode concurrently')
     ap.add_argument('--threads', type=int, default=6, help='node mode: decode threads per rank (ClipFeeder workers)')
     ap.add_argument('--seconds', type=float, default=8.0)
@@ -417,6 +547,9 @@ def main():
         args.height = 1080 if args.format == 'jpeg' else 1024
     if args.width is None:
         args.width = 1920 if args.format == 'jpeg' else 2048
+    if args.y4m:
+        args.out = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'y4m_pipeline.json')
+        return y4m_mode(args)
     if args.format == 'jpeg':
         return jpeg_mode(args)
     if args.node:

@@ -519,9 +519,81 @@ def tubes_leg(args):
     return rep
 
 
+def y4m_leg(args):
+    """`--leg y4m`: the Y4M output path at 420jpeg. `vps_bgr_to_yuv` by events, and `Y4mWriter` to a file on local disk and to a sink that
+    discards against `DeviceJpegWriter(entropy='device')` writing files, same process, alternating windows. The 'output' key of --out."""
+    import torch
+    from bench_input_pipeline import time_kernel
+    from vps_amd import hip, synth, y4m
+    from vps_amd import postprocess as pp
+    assert torch.cuda.is_available(), 'the conversion runs on the device'
+    dev = torch.device('cuda:0')
+    H, W = args.height, args.width
+    frames = [synth.synth_frame(H, W, seed=s, shift=(2 * s, s), noise=2.0).astype(np.uint8) for s in range(4)]       # BGR
+    frames = [np.pad(f, ((0, H - f.shape[0]), (0, W - f.shape[1]), (0, 0)), mode='edge') for f in frames]
+    imgs = [torch.from_numpy(np.ascontiguousarray(f)).to(dev) for f in frames]
+    nb = y4m.planar_bytes(H, W, '420jpeg')
+    rep = dict(mode='y4m-output', size=[H, W], sampling='420jpeg', range='limited', matrix='bt601', frames_per_window=args.frames, windows=args.repeats,
+               host_cpus=os.cpu_count(), csrc_sha16=hip.csrc_sha16(), y4m_MB_per_frame=round((nb + 6) / 1e6, 2))
+    moved = nb + 3 * H * W
+    npool = int(2 * (256 << 20) // moved) + 2
+    src = imgs + [imgs[k % 4].clone() for k in range(4, npool)]
+    dst = [torch.empty(nb, dtype=torch.uint8, device=dev) for _ in range(npool)]
+    res = time_kernel(lambda i: y4m.bgr_to_yuv(src[i], '420jpeg', 'limited', 'bt601', dst[i]), 4)
+    rep['vps_bgr_to_yuv_cache_resident'] = dict(res, inputs_cycled=4, working_set_MB=round(4 * moved / 1e6, 1), GBps_at_median=round(moved / res['ms_median'] / 1e6, 1))
+    res = time_kernel(lambda i: y4m.bgr_to_yuv(src[i], '420jpeg', 'limited', 'bt601', dst[i]), npool)
+    rep['vps_bgr_to_yuv_beyond_cache'] = dict(res, inputs_cycled=npool, working_set_MB=round(npool * moved / 1e6, 1), GBps_at_median=round(moved / res['ms_median'] / 1e6, 1))
+    rep['kernel_bytes_moved'] = moved
+    del src, dst
+
+    class Discard:
+        def write(self, b):
+            return len(b)
+
+        def flush(self):
+            pass
+
+    def window(kind):
+        with tempfile.TemporaryDirectory() as tmp:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if kind.startswith('jpeg'):
+                w = pp.DeviceJpegWriter(dev, workers=int(kind[4:]), slots=8, quality=90, entropy='device')
+                for f in range(args.frames):
+                    w.submit(imgs[f % 4], os.path.join(tmp, '%04d.jpg' % f))
+                w.close()
+                assert w.device_encoded == args.frames
+                mb = w.bytes_written / 1e6
+            else:
+                w = y4m.Y4mWriter(os.path.join(tmp, 'out.y4m') if kind == 'y4m_file' else Discard(), W, H, sampling='420jpeg', device=dev, slots=4)
+                for f in range(args.frames):
+                    w.submit(imgs[f % 4])
+                w.close()
+                assert w.frames == args.frames
+                mb = w.bytes / 1e6
+            dt = time.perf_counter() - t0
+        return args.frames / dt, mb
+
+    kinds = ('y4m_file', 'y4m_discard', 'jpeg1', 'jpeg4')
+    rates = {k: [] for k in kinds}
+    for k in kinds:                                                  # warm-up: ring slots, pinned staging, copy streams
+        window(k)
+    for _ in range(args.repeats):                                    # the writers alternate, so a busy host hits all of them
+        for k in kinds:
+            rates[k].append(window(k))
+    names = dict(y4m_file='Y4mWriter to a file on local disk', y4m_discard='Y4mWriter to a sink that discards',
+                 jpeg1="DeviceJpegWriter(entropy='device', workers=1) to files", jpeg4="DeviceJpegWriter(entropy='device', workers=4) to files")
+    rep['writer_frames_per_s'] = {k: dict(what=names[k], median=round(float(np.median([r[0] for r in rates[k]])), 1), min=round(min(r[0] for r in rates[k]), 1),
+                                          max=round(max(r[0] for r in rates[k]), 1), MB_written_per_window=round(rates[k][0][1], 1)) for k in kinds}
+    rep['writer_note'] = ('the clock runs from the first submit to the end of close(), file creation included; the JPEG frames are the RGB reading of the same '
+                          'arrays (the byte order does not change the work); the file goes to the temporary directory of the host, through its page cache')
+    rep['not_measured'] = 'a pipe to an encoder or a player; 444 and 420mpeg2; a detector clip with --overlay-video against the same clip without it'
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--leg', default='png', choices=['png', 'overlay', 'overlay_entropy', 'flow', 'tubes'])
+    ap.add_argument('--leg', default='png', choices=['png', 'overlay', 'overlay_entropy', 'flow', 'tubes', 'y4m'])
     ap.add_argument('--frames', type=int, default=30)
     ap.add_argument('--repeats', type=int, default=3, help='--leg flow / tubes / overlay_entropy: windows of --frames frames per writer figure (median and spread are reported)')
     ap.add_argument('--height', type=int, default=1024)
@@ -532,6 +604,12 @@ def main():
         args.out = os.path.join(ROOT, 'profiles', {'png': 'png_output_pipeline.json', 'overlay': 'overlay_output_pipeline.json',
                                                    'overlay_entropy': 'overlay_output_pipeline.json', 'flow': 'flow_output_pipeline.json',
                                                    'tubes': 'tubes_output_pipeline.json'}[args.leg])
+    if args.leg == 'y4m':                                            # the 'output' key of profiles/y4m_pipeline.json; 'input' is bench_input_pipeline.py --y4m
+        from bench_input_pipeline import merge_y4m_profile
+        rep = y4m_leg(args)
+        merge_y4m_profile(args.out or os.path.join(ROOT, 'profiles', 'y4m_pipeline.json'), 'output', rep)
+        print(json.dumps(rep))
+        return
     if args.leg == 'overlay_entropy':                                # a new key in the overlay report; the other keys stay as they are
         rep = overlay_entropy_leg(args)
         print(json.dumps(rep))

@@ -54,6 +54,13 @@ def parse_args(argv=None):
     ap.add_argument('--overlay', default=None, metavar='DIR', help='write DIR/<name>.jpg for every frame: the panoptic result blended over the frame (off by default; '
                     'keeps every decoded frame on the device until the maps are unified, 6 MB per frame at 1024x2048)')
     ap.add_argument('--overlay-quality', type=int, default=90)
+    ap.add_argument('--overlay-video', default=None, metavar='FILE.y4m', help='write the overlays of every video as one Y4M stream (YUV4MPEG2; with several '
+                    'videos the video\'s name goes in front of the extension), beside --overlay or without it (off by default)')
+    ap.add_argument('--overlay-video-sampling', default='420jpeg', choices=['420jpeg', '420mpeg2', '444'])
+    ap.add_argument('--video', default=None, metavar='FILE.y4m', help='run ONE clip from a Y4M file (ffmpeg -i in.mp4 -f yuv4mpegpipe in.y4m) instead of the '
+                    'dataset\'s image list: every frame is a result frame (no labelled-frame selection), the dataset files and the evaluation are not '
+                    'used; with --dry-run a synthetic clip of --dry-frames frames is written to a file of that name in the scratch directory')
+    ap.add_argument('--video-matrix', default='bt601', choices=['bt601', 'bt709'], help='--video: the colour matrix of the clip (Y4M has no tag for it)')
     ap.add_argument('--jpeg-entropy', default='host', choices=['host', 'device'],
                     help='where the JPEG files of --overlay and --flow are Huffman-coded; the files are the same (default host)')
     ap.add_argument('--overlay-alpha', type=int, default=128, help='weight of the colour map, 0..256')
@@ -106,6 +113,18 @@ def make_dry_run_artefacts(args, tmp):
     args.data_root = root
     args.out = os.path.join(tmp, 'work_dirs', 'cityscapes_vps', 'fusetrack_vpct', args.mode + '.pkl')
     args.n_video, args.nframes_span_test = args.dry_videos, args.dry_frames
+    if args.video and not torch.cuda.is_available() and not args.check_only:
+        raise SystemExit('--dry-run --video writes its clip through Y4mWriter, which converts on the device: no device here (only --check-only runs without one)')
+    if args.video and torch.cuda.is_available():
+        # the clip of --video: the frames of video 0 through the product's own writer (converted on the device, so only with one)
+        from vps_amd.y4m import Y4mWriter
+        args.video = os.path.join(tmp, os.path.basename(args.video))
+        w = Y4mWriter(args.video, W, H, fps=(17, 1), sampling='420jpeg')
+        for f in range(args.dry_frames):
+            fr = synth.synth_frame(H, W, seed=0, shift=(2 * f, f), noise=2.0 if f else 0.0).astype(np.uint8)
+            fr = np.pad(fr, ((0, H - fr.shape[0]), (0, W - fr.shape[1]), (0, 0)), mode='edge')      # late frames are cropped at the noise field's edge
+            w.submit(torch.from_numpy(np.ascontiguousarray(fr)).cuda())
+        w.close()
     return args
 
 
@@ -130,8 +149,10 @@ def run(args, tmp):
         args = make_dry_run_artefacts(args, tmp)
     import vps_amd
     from vps_amd import nhwc
-    for f in (args.checkpoint, args.flownet_checkpoint, os.path.join(args.data_root, 'im_all_info_%s_city_vps.json' % args.mode),
-              os.path.join(args.data_root, 'panoptic_im_%s_city_vps.json' % args.mode)):
+    dataset_files = [os.path.join(args.data_root, 'im_all_info_%s_city_vps.json' % args.mode), os.path.join(args.data_root, 'panoptic_im_%s_city_vps.json' % args.mode)]
+    if args.video:
+        dataset_files = [args.video] if not (args.dry_run and args.check_only) else []
+    for f in [args.checkpoint, args.flownet_checkpoint] + dataset_files:
         if not os.path.exists(f):
             print(json.dumps(dict(report, error='missing artefact: %s (the reference fetches it with download_weights.sh / the dataset README; '
                                                 'use --dry-run for synthetic stand-ins)' % f)))
@@ -147,11 +168,27 @@ def run(args, tmp):
     report['checkpoint'] = dict(file=args.checkpoint, loaded=rep.get('loaded'), missing=rep.get('missing'), unexpected=rep.get('unexpected'),
                                 classes=list(model.CLASSES))
     # ---- the dataset list (cityscapes_vps.py:137-148: the previous frame is the reference, a video's first frame its own) -----------
-    info = json.load(open(os.path.join(args.data_root, 'im_all_info_%s_city_vps.json' % args.mode)))['images']
-    img_prefix = os.path.join(args.data_root, args.mode, 'img_all')
-    im_jsons = json.load(open(os.path.join(args.data_root, 'panoptic_im_%s_city_vps.json' % args.mode)))
+    reader = None
+    if args.video:
+        # ONE clip from a Y4M file: frame f is '<stem>_<f, six digits>.png' in every output, every frame is a result frame, one video
+        from run_vps_synthetic import CATEGORIES
+        from vps_amd.y4m import Y4mReader
+        stem, nfr = os.path.splitext(os.path.basename(args.video))[0], 0
+        if os.path.exists(args.video):
+            reader = Y4mReader(args.video)
+            nfr = len(reader)
+            report['video'] = dict(file=args.video, frames=nfr, size=[reader.info.H, reader.info.W], sampling=reader.info.sampling, range=reader.info.range,
+                                   fps=list(reader.info.fps), dropped_partial_frames=reader.dropped, matrix=args.video_matrix)
+        info = [dict(id=f + 1, file_name='%s_%06d.png' % (stem, f)) for f in range(nfr)]
+        img_prefix, categories = os.path.dirname(os.path.abspath(args.video)), CATEGORIES
+        im_jsons = dict(images=[dict(id=x['file_name'][:-4], file_name=x['file_name']) for x in info], categories=categories)
+        args.n_video, args.nframes_span_test = 1, max(nfr, 1)
+    else:
+        info = json.load(open(os.path.join(args.data_root, 'im_all_info_%s_city_vps.json' % args.mode)))['images']
+        img_prefix = os.path.join(args.data_root, args.mode, 'img_all')
+        im_jsons = json.load(open(os.path.join(args.data_root, 'panoptic_im_%s_city_vps.json' % args.mode)))
+        categories = im_jsons['categories']
     names = sorted(x['file_name'] for x in im_jsons['images'])
-    categories = im_jsons['categories']
     span = args.nframes_span_test
     report['dataset'] = dict(frames=len(info), videos=len(info) // max(span, 1), labelled_frames=len(names), img_prefix=img_prefix)
     if args.check_only:
@@ -164,7 +201,12 @@ def run(args, tmp):
     model.ensure_packed(dev)
     prep = DeviceImagePrep(**cfg.img_norm_cfg, size_divisor=32, img_scale=(2048, 1024), device=dev)
     files = [os.path.join(img_prefix, x['file_name']) for x in info]
-    feeder = ClipFeeder(files, prep, workers=args.png_workers, keep_frames=bool(args.overlay)).start()
+    keep = bool(args.overlay or args.overlay_video)
+    if reader is not None:
+        assert len(reader) > 0, '%s holds no complete frame' % args.video
+        feeder = ClipFeeder(reader, prep, workers=args.png_workers, keep_frames=keep, y4m_matrix=args.video_matrix).start()
+    else:
+        feeder = ClipFeeder(files, prep, workers=args.png_workers, keep_frames=keep).start()
     res = dict(all_names=[], all_ssegs=[], all_panos=[], all_pano_cls_inds=[], all_pano_obj_ids=[], all_frames=[])
     flow_writer = None
     if args.flow:
@@ -178,6 +220,8 @@ def run(args, tmp):
             ref = feeder(idx - 1) if idx % span > 0 else img
             nxt = idx + 1 if idx + 1 < len(info) else None
             meta = dict(feeder.meta(idx), iid=im['id'])       # filename, ori_shape, img_shape, pad_shape, scale_factor, flip + the video index
+            if reader is not None:
+                meta['dataset'] = 'cityscapes_vps'       # the tracking detector checks for Cityscapes-VPS file names otherwise; the clip's is '<path>#<t>'
             # the next pair is known: its image-only stages are announced to the detector (the drop-in's own clip pipelining)
             pf = (feeder(nxt), img) if (nxt is not None and nxt % span > 0) else None
             result = model.simple_test(img, [meta], rescale=True, ref_img=[ref], prefetch=pf)
@@ -185,7 +229,7 @@ def run(args, tmp):
             res['all_pano_cls_inds'].append(result[2]['panoptic_cls_inds'].cpu().numpy())
             res['all_pano_obj_ids'].append(result[2]['panoptic_det_obj_ids'].cpu().numpy())
             res['all_names'].append(os.path.basename(files[idx]))
-            if args.overlay:
+            if keep:
                 res['all_frames'].append(feeder.frame(idx))       # the decoded BGR frame the feeder holds anyway
             if flow_writer is not None:
                 flow_writer.submit(result[2]['flow'], flow_name(args.flow, files[idx], args.flow_format))
@@ -208,7 +252,9 @@ def run(args, tmp):
         from run_vps_synthetic import ColorGenerator          # stand-in with the same get_color(cat_id) contract (panopticapi is absent offline)
         gen = ColorGenerator({c['id']: c for c in categories})
     kw = {}
-    if args.dry_run:
+    if args.video:
+        kw = dict(labeled_fid=0, lambda_=1, nframes_per_video=len(names))                  # every frame, one video
+    elif args.dry_run:
         kw = dict(labeled_fid=args.dry_label_first, lambda_=5, nframes_per_video=len(names) // max(args.n_video, 1))
     if args.device_png:
         from vps_amd.postprocess import DevicePngWriter
@@ -223,18 +269,25 @@ def run(args, tmp):
         tb = kw['tubes'].result()
         report['tubes'] = dict(file=os.path.join(output_dir, 'tubes.json'), videos=len(tb['videos']), tracks=sum(len(v['tracks']) for v in tb['videos']))
         kw['tubes'].close()
-    if args.overlay:
+    if keep:
         from run_vps_synthetic import ColorGenerator
         from vps_amd.postprocess import write_overlays
         order = sorted(range(len(res['all_names'])), key=lambda i: res['all_names'][i])                # the order of pred_pans_2ch
+        vfiles = []
+        vkw = dict(video=args.overlay_video, video_sampling=args.overlay_video_sampling, video_files=vfiles) if args.overlay_video else {}
         ov = write_overlays(pred_pans_2ch, [res['all_frames'][i] for i in order], [res['all_names'][i] for i in order], args.overlay,
                             ColorGenerator({c['id']: c for c in categories}), span, device=dev, quality=args.overlay_quality, alpha=args.overlay_alpha,
-                            entropy=args.jpeg_entropy)
+                            entropy=args.jpeg_entropy, **vkw)
+    if args.overlay_video:                                  # keys of their own: without the options the report is what it was
+        report['overlay_video'] = dict(files=vfiles, sampling=args.overlay_video_sampling, bytes=sum(os.path.getsize(f) for f in vfiles))
+    if args.overlay:
         report['overlay'] = dict(dir=args.overlay, files=len(ov), quality=args.overlay_quality, alpha=args.overlay_alpha, entropy=args.jpeg_entropy)
+    if reader is not None:
+        report['video']['native_y4m'] = feeder.native_y4m
     report['run'] = dict(frames=len(info), seconds=round(dt, 3), frames_per_s=round(len(info) / dt, 2), decodes=feeder.decodes, output_dir=output_dir,
                          png_files=len(os.listdir(os.path.join(output_dir, 'pan_pred'))))
-    truth_dir, gt_json = args.truth_dir, args.pan_gt_json
-    if args.dry_run:
+    truth_dir, gt_json = (None, None) if args.video else (args.truth_dir, args.pan_gt_json)       # a clip from a file has no ground truth
+    if args.dry_run and not args.video:
         # ground truth = this run's own prediction, written in the ground-truth layout: the reference's metric must come out as 100
         truth_dir = os.path.join(args.data_root, args.mode, 'panoptic_video')
         os.makedirs(truth_dir, exist_ok=True)

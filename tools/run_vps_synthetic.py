@@ -104,11 +104,14 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg
     return res, time.perf_counter() - t0
 
 
-def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_png=False, overlay=None, tubes=False, jpeg_entropy='host'):
+def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_png=False, overlay=None, tubes=False, jpeg_entropy='host',
+                overlay_video=None):
     """test_vpq.py:178-198 with the device-side unifier / converter / asynchronous writer (`device_png`: the PNGs are filtered and
     deflated on the device too, postprocess.DevicePngWriter). `overlay` = (directory, quality, alpha): an overlay JPEG of EVERY frame,
     blended and transformed on the device (postprocess.write_overlays). `tubes`: tubes.json beside pred.json, the COCO run-length
-    encoding, box and area of every tracked instance in every labelled frame (vps_amd.tubes)"""
+    encoding, box and area of every tracked instance in every labelled frame (vps_amd.tubes). `overlay_video` = (FILE.y4m, sampling):
+    the same overlays as one Y4M stream per video (y4m.Y4mWriter), beside the JPEGs or, without `overlay`, instead of them; its
+    'files' entry receives the streams' names"""
     from vps_amd.postprocess import DevicePngWriter, PanopticUnifier, inference_panoptic_video, write_overlays
     unifier = PanopticUnifier(dev, 19, 9)
     two = unifier.get_unified_pan_result(res['all_ssegs'], res['all_panos'], res['all_pano_cls_inds'], obj_ids=res['all_pano_obj_ids'],
@@ -128,13 +131,15 @@ def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_pn
         collector.close()
     if writer is not None:
         writer.close()
-    if overlay:
+    if overlay or overlay_video:
         # (synth_frame crops the late, far-shifted frames of a clip at the edge of its noise field while img_meta keeps the nominal
         # size: such a frame is padded back to the size of its map with its edge pixels)
         frames = {n: np.pad(f, ((0, two[n].shape[0] - f.shape[0]), (0, two[n].shape[1] - f.shape[1]), (0, 0)), mode='edge')
                   for n, f in zip(res['all_names'], res['all_frames'])}
-        write_overlays(pred_pans_2ch, [frames[k] for k in keys], keys, overlay[0], ColorGenerator(cats), len(keys) // max(videos, 1), device=dev,
-                       quality=overlay[1], alpha=overlay[2], entropy=jpeg_entropy)
+        ov = overlay or (None, 90, overlay_video['alpha'])
+        vkw = dict(video=overlay_video['file'], video_sampling=overlay_video['sampling'], video_files=overlay_video['files']) if overlay_video else {}
+        write_overlays(pred_pans_2ch, [frames[k] for k in keys], keys, ov[0], ColorGenerator(cats), len(keys) // max(videos, 1), device=dev,
+                       quality=ov[1], alpha=ov[2], entropy=jpeg_entropy, **vkw)
     return names, pans, pj
 
 
@@ -170,6 +175,9 @@ def main():
     ap.add_argument('--overlay', default=None, metavar='DIR', help='write DIR/<name>.jpg for every frame: the panoptic result blended over the frame (off by default)')
     ap.add_argument('--overlay-quality', type=int, default=90)
     ap.add_argument('--overlay-alpha', type=int, default=128, help='weight of the colour map, 0..256')
+    ap.add_argument('--overlay-video', default=None, metavar='FILE.y4m', help='write the overlays of every video as one Y4M stream (YUV4MPEG2; with several '
+                    'videos the video\'s name goes in front of the extension), beside --overlay or without it (off by default)')
+    ap.add_argument('--overlay-video-sampling', default='420jpeg', choices=['420jpeg', '420mpeg2', '444'])
     ap.add_argument('--jpeg-entropy', default='host', choices=['host', 'device'],
                     help='where the JPEG files of --overlay and --flow are Huffman-coded; the files are the same (default host)')
     ap.add_argument('--tubes', action='store_true', help='write pred/tubes.json: run-length encoded masks, boxes and areas of every tracked instance (off by default)')
@@ -180,12 +188,13 @@ def main():
     dev = torch.device('cuda:0')
     labeled_fid, lambda_ = 20, 5
     overlay = (args.overlay, args.overlay_quality, args.overlay_alpha) if args.overlay else None
+    overlay_video = dict(file=args.overlay_video, sampling=args.overlay_video_sampling, files=[], alpha=args.overlay_alpha) if args.overlay_video else None
     nper = len(range(labeled_fid // lambda_, args.frames, lambda_))
     flow = (args.flow, args.flow_format, args.flow_max_rad) if args.flow else None
     res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated, flow, args.jpeg_entropy)
     t0 = time.perf_counter()
     names, pans, pj = postprocess(res, os.path.join(args.out, 'pred'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png, overlay, args.tubes,
-                                  args.jpeg_entropy)
+                                  args.jpeg_entropy, overlay_video)
     dpost = time.perf_counter() - t0
     pred = (pans, pj)
     gt = pred
@@ -203,6 +212,8 @@ def main():
                   pq_per_window={str(k): round(100 * score[k]['pq'], 4) for k in (1, 2, 3, 4)},
                   seconds=dict(model=round(dt, 3), postprocess_and_png=round(dpost, 3), eval=round(deval, 3)),
                   frames_per_s_upload_prep_model_sequential=round(args.videos * args.frames / dt, 2))
+    if overlay_video:                                   # a key of its own: without the option the report is what it was
+        report['overlay_video'] = dict(files=overlay_video['files'], sampling=args.overlay_video_sampling)
     with open(os.path.join(args.out, 'report.json'), 'w') as f:
         json.dump(report, f, indent=1)
     print(json.dumps(report))

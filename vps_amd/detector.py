@@ -304,7 +304,8 @@ class PanopticFuseTrack(HipModule):
             ref_img = ref_img[0]
         meta = img_meta[0]
         if self.with_track:
-            assert 'city' in meta['filename'] and 'iid' in meta
+            # (the reference's check that it is fed Cityscapes-VPS frames; a clip that has no such file names says so: meta['dataset'])
+            assert ('city' in meta['filename'] or meta.get('dataset') == 'cityscapes_vps') and 'iid' in meta
         iid = meta.get('iid', -1)          # PanopticFuse runs on image pairs without a video index
         is_first = (iid % 10000) == 1
         _, _, H, W = img.shape

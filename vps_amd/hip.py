@@ -36,6 +36,7 @@ SYMBOLS = [
     'vps_jpeg_scan_bound', 'vps_jpeg_encode_scan', 'vps_jpeg_wrap',
     'vps_flow_max_radius', 'vps_flow_colour',
     'vps_rle_runs', 'vps_rle_runs_ws', 'vps_rle_band_rows', 'vps_rle_strings', 'vps_rle_strings_bound',
+    'vps_y4m_info', 'vps_y4m_frame_header', 'vps_y4m_write_header', 'vps_yuv_to_bgr', 'vps_bgr_to_yuv', 'vps_yuv_tile',
 ]
 
 
@@ -65,6 +66,13 @@ class Tensor4(Structure):
 class PanInst(Structure):
     _fields_ = [('sx0', c_int32), ('sy0', c_int32), ('sx1', c_int32), ('sy1', c_int32), ('seg_ch', c_int32),
                 ('bx1', c_int32), ('by1', c_int32), ('bx2', c_int32), ('by2', c_int32), ('mask_idx', c_int32)]
+
+
+class Y4mDesc(Structure):
+    """vps_y4m_desc: what `vps_y4m_info` reports about a YUV4MPEG2 stream header"""
+    _fields_ = [('W', c_int32), ('H', c_int32), ('CW', c_int32), ('CH', c_int32), ('sampling', c_int32), ('range', c_int32),
+                ('fps_num', c_int32), ('fps_den', c_int32), ('aspect_num', c_int32), ('aspect_den', c_int32), ('interlace', c_int32),
+                ('header_bytes', c_int32), ('frame_bytes', c_int64)]
 
 
 _lib = None
@@ -209,6 +217,10 @@ def load():
         h.vps_rle_strings.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
         h.vps_rle_strings_bound.restype = c_int64
         h.vps_rle_strings_bound.argtypes = [c_int, c_int]
+        h.vps_y4m_info.restype = h.vps_y4m_frame_header.restype = h.vps_y4m_write_header.restype = c_int
+        h.vps_y4m_info.argtypes = [c_void_p, c_int64, POINTER(Y4mDesc)]
+        h.vps_y4m_frame_header.argtypes = [c_void_p, c_int64, POINTER(c_int32)]
+        h.vps_y4m_write_header.argtypes = [POINTER(Y4mDesc), c_void_p, c_int64, POINTER(c_int32)]
     lib.vps_rle_runs.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]
     lib.vps_rle_runs_ws.restype = c_int64
     lib.vps_rle_runs_ws.argtypes = [c_int, c_int]
@@ -220,6 +232,9 @@ def load():
     lib.vps_jpeg_encode_scan.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]
     lib.vps_flow_max_radius.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.vps_flow_colour.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    lib.vps_yuv_to_bgr.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]
+    lib.vps_bgr_to_yuv.argtypes = [c_void_p, c_int, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]
+    lib.vps_yuv_tile.argtypes = [POINTER(c_int32), POINTER(c_int32)]
     lib.vps_png_reconstruct_ws.argtypes = [c_int, c_int, c_int, POINTER(c_int64)]
     lib.vps_png_reconstruct.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]
     lib.vps_png_reconstruct_block_rows.argtypes = []

@@ -14,6 +14,7 @@ the decoded image; restated from the published resize.cpp, no cv2 here to pin it
 lossless, so the arrays equal cv2's for the datasets of the path) and decode every file ONCE — frame t's `ref_filename` is frame
 t-1's `filename`. No CPU path for the transforms: the HIP library must load."""
 import ctypes
+import os
 import os.path as osp
 
 import warnings
@@ -22,6 +23,7 @@ import numpy as np
 import torch
 
 from . import hip
+from . import y4m as _y4m
 
 
 class DeviceImagePrep:
@@ -141,7 +143,11 @@ class ClipFeeder:
     / palette PNG) go through `imread` and one copy into the staging buffer (`fallback_decodes`). `png='device'` (opt-in) splits a PNG the
     same way: the worker only inflates (`vps_png_inflate`), the device un-filters and swaps to BGR (`vps_png_reconstruct`, `native_png_device`).
     The ring's slots are sized from the FIRST file; a later PNG whose scanlines do not fit a slot (RGBA behind an RGB first file) is decoded by
-    the worker as with png='host' - the bytes are the same, only `native_png_device` stays lower. What did NOT work (measured on the GPU box): PIL decode threads - they hold the interpreter lock
+    the worker as with png='host' - the bytes are the same, only `native_png_device` stays lower. `files` may also be ONE `.y4m` path
+    (or a `y4m.Y4mReader`): `len(feeder)` is its frame count, a worker reads frame t's planes straight into a pinned slot of
+    `frame_bytes` (1.5 bytes per pixel at 4:2:0, no decode), the consumer uploads them and `vps_yuv_to_bgr` makes the BGR frame
+    (`native_y4m`; `y4m_matrix` 'bt601' / 'bt709', the container has no tag for it); `meta(t)['filename']` is '<path>#<t>'. A host
+    stand-in `prep` is refused for such a clip: the conversion exists on the device only. What did NOT work (measured on the GPU box): PIL decode threads - they hold the interpreter lock
     for long stretches and beside a main thread that launches ~560 kernels per frame deliver 6 frames/s; forked decode processes -
     the fork of a process that maps 30 GB of device memory stalls (1.4 frames/s). A prepared frame is kept until the consumer asks
     for a frame two positions later (frame t is frame t+1's reference), so the same tensor OBJECT serves as `img` of frame t and
@@ -152,10 +158,21 @@ class ClipFeeder:
         feeder.close()
     """
 
-    def __init__(self, files, prep, workers=4, ahead=None, png='host', keep_frames=False):
+    def __init__(self, files, prep, workers=4, ahead=None, png='host', keep_frames=False, y4m_matrix='bt601'):
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         assert png in ('host', 'device'), "png: 'host' (decode on the worker) or 'device' (inflate on the worker, un-filter on the device)"
+        self._y4m, self._y4m_own, self.y4m_matrix = None, False, y4m_matrix
+        if isinstance(files, _y4m.Y4mReader) or (isinstance(files, (str, os.PathLike)) and str(files).lower().endswith('.y4m')):
+            # ONE video file instead of a list of image files: frame t is '<path>#<t>'. The conversion has no host twin: a host
+            # stand-in for `prep` is refused here, not served by another arithmetic.
+            if prep.device.type != 'cuda':
+                raise hip.VpsHipError('ClipFeeder: a .y4m clip is converted on the device (vps_yuv_to_bgr); prep.device is %s and there is no host path' % prep.device)
+            if y4m_matrix not in _y4m.MATRICES:
+                raise ValueError('y4m_matrix is one of %s, got %r' % (', '.join(_y4m.MATRICES), y4m_matrix))
+            self._y4m_own = not isinstance(files, _y4m.Y4mReader)
+            self._y4m = _y4m.Y4mReader(files) if self._y4m_own else files
+            files = ['%s#%d' % (self._y4m.path, t) for t in range(len(self._y4m))]
         self.files, self.prep, self.png = list(files), prep, png
         self.workers = int(workers)
         self.ahead = int(ahead) if ahead is not None else 2 * self.workers      # decoded frames in flight beyond the consumer
@@ -171,6 +188,7 @@ class ClipFeeder:
         self.decodes = 0
         self.native_jpeg = 0        # frames whose entropy decode ran in the library and whose pixels the device reconstructed
         self.native_png_device = 0  # frames a worker only inflated and whose scanlines the device un-filtered (png='device')
+        self.native_y4m = 0         # frames a worker only read from a .y4m file and whose planes the device converted to BGR
         self.fallback_decodes = 0   # frames that went through `imread` (files the native decoders do not take)
         self.out_of_window = 0      # requests that found their frame neither prepared nor in flight (decoded on the spot)
         self.stats = dict(wait_for_decode_s=0.0, upload_prep_s=0.0)      # where the consumer's time in __call__ went
@@ -228,6 +246,16 @@ class ClipFeeder:
         stage[:img.nbytes].copy_(torch.from_numpy(img).reshape(-1))
         return img.shape[0], img.shape[1], 'imread'
 
+    def _read_y4m(self, t, slot):
+        """worker thread: frame t of the .y4m clip -> staging slot, the planes as they lie in the file (no decode at all); tag = its `Y4mInfo`"""
+        self._y4m.readinto(t, self._stage[slot])
+        return self._y4m.info.H, self._y4m.info.W, self._y4m.info
+
+    def _job(self, t, slot):
+        if self._y4m is not None:
+            return self._pool.submit(self._read_y4m, t, slot)
+        return self._pool.submit(self._decode, self.files[t], slot)
+
     def _take_slot(self):
         slot = self._free.popleft()
         if self._events[slot] is not None:
@@ -236,6 +264,8 @@ class ClipFeeder:
         return slot
 
     def _submit_until(self, t_hi):
+        if not self._stage and self.files and self._y4m is not None:
+            self._slots(self._y4m.info.frame_bytes)
         if not self._stage and self.files:
             from PIL import Image
             with Image.open(self.files[0]) as im:                                # header only: the frame size of the clip
@@ -261,7 +291,7 @@ class ClipFeeder:
             if not self._free:
                 break
             slot = self._take_slot()
-            self._pending[t] = (self._pool.submit(self._decode, self.files[t], slot), slot)
+            self._pending[t] = (self._job(t, slot), slot)
             self._next += 1
 
     def start(self, t=0):
@@ -305,7 +335,7 @@ class ClipFeeder:
             if not self._free:
                 raise RuntimeError('ClipFeeder: frame %d requested outside the decode window with every staging buffer in flight' % t)
             slot = self._take_slot()
-            ent = (self._pool.submit(self._decode, self.files[t], slot), slot)
+            ent = (self._job(t, slot), slot)
         fut, slot = ent
         c0 = time.perf_counter()
         H, W, tag = fut.result()
@@ -313,13 +343,14 @@ class ClipFeeder:
         self.stats['wait_for_decode_s'] += c1 - c0
         self.decodes += 1
         dev = self.prep.device
-        jpeg, png = isinstance(tag, JpegInfo), isinstance(tag, PngInfo)
+        jpeg, png, y4 = isinstance(tag, JpegInfo), isinstance(tag, PngInfo), isinstance(tag, _y4m.Y4mInfo)
         self.native_jpeg += jpeg
         self.native_png_device += png
+        self.native_y4m += y4
         self.fallback_decodes += tag == 'imread'
         # a JPEG's slot holds coefficients + tables (for 4:2:0 the size of the BGR frame): uploaded as they are, the frame is rebuilt there
         src = self._stage[slot][:tag.coef_bytes + JPEG_QT_BYTES] if jpeg else self._stage[slot][:tag.scan_bytes] if png \
-            else self._stage[slot][:H * W * 3].view(H, W, 3)
+            else self._stage[slot][:tag.frame_bytes] if y4 else self._stage[slot][:H * W * 3].view(H, W, 3)
         if dev.type == 'cuda':
             d = src.to(dev, non_blocking=True)
             ev = torch.cuda.Event(); ev.record()
@@ -328,6 +359,8 @@ class ClipFeeder:
                 d = jpeg_reconstruct(d, tag)
             elif png:
                 d = png_reconstruct(d, tag.H, tag.W, tag.C)
+            elif y4:
+                d = _y4m.yuv_to_bgr(d, tag, self.y4m_matrix)
         else:
             d = src.numpy().copy()                 # host stand-in (tests): own copy, the slot goes back to the ring
         out, img_shape, pad_shape, sf = self.prep.prep(d)
@@ -355,6 +388,8 @@ class ClipFeeder:
             fut.cancel()
         self._pool.shutdown(wait=True)
         self._pending = {}
+        if self._y4m_own:
+            self._y4m.close()
 
 
 JPEG_QT_BYTES = 3 * 64 * 2         # the three quantisation tables (uint16, natural order) travel behind the coefficients

@@ -710,25 +710,71 @@ def overlay_name(save_folder, name):
 
 
 def write_overlays(pred_pans_2ch, frames, names, out_dir, color_generator, nframes_per_video, device='cuda', alpha=128, quality=90,
-                   writer=None, entropy='host'):
+                   writer=None, entropy='host', video=None, video_sampling='420jpeg', video_fps=(30, 1), video_files=None):
     """an overlay JPEG of EVERY frame: `pred_pans_2ch` (the unified 3-channel maps, host or device) are painted per video by
     `TrackConverter.convert_device` (a track keeps its colour through its video), blended over `frames` (BGR uint8 [H,W,3], host or
     device, same order) by `render_overlay` and written as `out_dir/<name>.jpg` through a `DeviceJpegWriter` (the caller's, or one made
     and closed here, with `entropy` 'host' or 'device'). `color_generator`: its own instance - the colours of pred.json are not touched.
-    Returns the file names."""
+    Returns the file names.
+    video='FILE.y4m' (default None: nothing else happens): the same images also go, video by video, to one Y4M stream each through a
+    `y4m.Y4mWriter` (`video_sampling`, `video_fps`; limited range, bt601): `video` itself for a single video, else the video's name
+    (`video_name_of` its frames' names) inserted in front of the extension, `overlay_video_name`. `video_files`: a list that receives
+    the streams' names. With `out_dir=None` only the streams are written and the return value is their names."""
     assert len(pred_pans_2ch) == len(frames) == len(names)
-    own = writer is None
+    jpegs = out_dir is not None
+    assert jpegs or video is not None, 'nothing to write: out_dir and video are both None'
+    own = writer is None and jpegs
     writer = DeviceJpegWriter(device, quality=quality, entropy=entropy) if own else writer
     conv = TrackConverter(device)
-    out = []
+    out, videos = [], [] if video_files is None else video_files
+    nvideos = (len(pred_pans_2ch) + nframes_per_video - 1) // nframes_per_video
     for v0 in range(0, len(pred_pans_2ch), nframes_per_video):
         _, pans_dev, _ = conv.convert_device(pred_pans_2ch[v0:v0 + nframes_per_video], color_generator)
-        for j, pan in enumerate(pans_dev):
-            out.append(overlay_name(out_dir, names[v0 + j]))
-            writer.submit(render_overlay(frames[v0 + j], pan, alpha), out[-1])
+        vw = None
+        try:
+            for j, pan in enumerate(pans_dev):
+                img = render_overlay(frames[v0 + j], pan, alpha)
+                if jpegs:
+                    out.append(overlay_name(out_dir, names[v0 + j]))
+                    writer.submit(img, out[-1])
+                if video is not None:
+                    if vw is None:
+                        from .y4m import Y4mWriter
+                        vname = video_name_of(names[v0:v0 + nframes_per_video], v0 // nframes_per_video)
+                        videos.append(overlay_video_name(video, vname, nvideos, taken=videos))
+                        vw = Y4mWriter(videos[-1], int(img.shape[1]), int(img.shape[0]), fps=video_fps, sampling=video_sampling, device=img.device,
+                                       order='rgb')
+                    vw.submit(img)
+        finally:
+            if vw is not None:
+                vw.close()
     if own:
         writer.close()
-    return out
+    return out if jpegs else videos
+
+
+def video_name_of(names, k):
+    """the name of video k from the names of its frames: what their base names have in common, cut back to a whole `_` / `-` separated
+    field ('0005_0025_frankfurt_..', '0005_0026_frankfurt_..' -> '0005'); 'v<k, three digits>' when they share no whole field"""
+    stems = [os.path.splitext(os.path.basename(n))[0] for n in names]
+    common = os.path.commonprefix(stems)
+    if not all(s == common or s[len(common)] in '_-' for s in stems):     # the prefix ends inside a field
+        cut = max(common.rfind('_'), common.rfind('-'))
+        common = common[:cut] if cut > 0 else ''
+    return common.rstrip('_-') or 'v%03d' % k
+
+
+def overlay_video_name(video, vname, nvideos, taken=()):
+    """the Y4M file of the video called `vname`: `video` itself for a single video, else DIR/<stem>.<vname><ext> (with a counter behind
+    the name when an earlier video of the call has the same one)"""
+    if nvideos <= 1:
+        return video
+    stem, ext = os.path.splitext(video)
+    name, n = '%s.%s%s' % (stem, vname, ext), 1
+    while name in taken:
+        n += 1
+        name = '%s.%s-%d%s' % (stem, vname, n, ext)
+    return name
 
 
 def png_name(save_folder, name):
