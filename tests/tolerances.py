@@ -46,7 +46,29 @@ the floor. The figures behind them (absolute, measured on the tests' inputs; HEA
   vps_maskroi_select boxes, n = 37        6.8e-5                        2       1.22e-4 (ulp of width 1024)   1.37e-4
   vps_maskroi_select boxes, n = 1024      9.1e-5                        2       1.22e-4                       1.83e-4
   select -> nms -> finish chain, n = 37   7.9e-5                        2       1.22e-4                       1.58e-4
-  (rows of <= 64 columns keep the project's 1e-5 / 1e-6 of tests/test_hip_ops.py)"""
+  (rows of <= 64 columns keep the project's 1e-5 / 1e-6 of tests/test_hip_ops.py)
+
+Kernel-level tests of the panoptic combine and of MaskRemoval (tests/test_pan_ops_gpu.py against tests/pan_restate.py) compare maps and
+kept lists exactly. Two bounds decide WHERE: a pixel of a random-input combine case is compared exactly unless the float64 margin
+between its two largest logits lies in (0, bound] (then the map must name a channel within bound of the maximum; at most 0.2 % of a
+case's pixels may be excluded), and an occupancy pixel of MaskRemoval is compared unless a kept box's resized logit is within
+unsure_bound of zero. Both are DERIVED by the tests from their inputs: the factor times the distance of the float32 restatement from
+the float64 one, never below the floor (absolute figures, measured on the tests' inputs; PAN_OPS_MEASURED below):
+
+  kernel, case                              float32 restatement vs float64   factor   floor (1 ulp of max |logit|)   bound used   excluded pixels
+  combine, k5      (13x22 up 4, k 5)            1.28e-6                        4       9.5e-7                         5.11e-6      0 of 4576
+  combine, up2_k70 (20x50 up 2, k 70)           9.07e-7                        4       9.5e-7                         3.63e-6      0 of 4000
+  combine, up1_k3  (24x40 up 1, k 3)            3.73e-8                        4       9.5e-7                         the floor    0 of 960
+  combine, up8_k12 (5x9 up 8, k 12)             8.79e-7                        4       9.5e-7                         3.52e-6      0 of 2880
+  combine, k244    (13x22 up 4, k 244)          1.30e-6                        4       9.5e-7                         5.19e-6      0 of 4576
+  combine, c33_k12 (33 classes, k 12)           1.10e-6                        4       9.5e-7                         4.41e-6      0 of 4576
+  combine, s7_k12  (S = 7, permuted masks)      1.02e-6                        4       9.5e-7                         4.10e-6      0 of 4576
+  MaskRemoval resized logits, n1                9.69e-8                        4       -                              3.87e-7      0 unsure pixels
+  MaskRemoval resized logits, n12_c3            6.72e-7                        4       -                              2.69e-6      0
+  MaskRemoval resized logits, n40_c2            5.38e-7                        4       -                              2.15e-6      0
+  MaskRemoval resized logits, n40_c1            6.39e-7                        4       -                              2.55e-6      0
+  MaskRemoval, thr30 / thr31 (all-ones masks)   0                              4       -                              0            0
+  (the single-box test of tests/test_hip_ops.py allows 7e-6 max|m28| = about 5e-5 around zero: twenty times these)"""
 
 STAGE = dict(flow=5e-5, fpn=5e-5, neck=2e-3, fcn_score=2e-3, cls_score=2e-3, bbox_pred=2e-3, score=2e-3)
 STAGE_R101 = dict(neck=1e-2, fcn_score=1e-2, cls_score=1e-2, bbox_pred=1e-2, score=1e-2)      # the stages behind the FPN of the 101-layer model
@@ -58,6 +80,10 @@ CONDITIONED_BF16X3 = 5e-4
 MAP = dict(sem=1e-3, pan=1e-3, pan_dense=5e-3, pan_config5=1.5e-2)
 # what the derived bounds of tests/test_head_ops_gpu.py were derived FROM (a record: the tests recompute them from their inputs)
 HEAD_OPS_MEASURED = dict(softmax_f32_vs_f64=1.6e-7, log_softmax_f32_vs_f64=3.8e-6, maskroi_boxes_f32_vs_f64=9.1e-5, maskroi_chain_boxes_f32_vs_f64=7.9e-5)
+# the same record for tests/test_pan_ops_gpu.py: the largest float32-vs-float64 distance of the restated logits per case / list
+PAN_OPS_MEASURED = dict(combine_f32_vs_f64=dict(k5=1.28e-6, up2_k70=9.07e-7, up1_k3=3.73e-8, up8_k12=8.79e-7, k244=1.30e-6, c33_k12=1.10e-6, s7_k12=1.02e-6),
+                        removal_resized_f32_vs_f64=dict(n1=9.69e-8, n12_c3=6.72e-7, n40_c2=5.38e-7, n40_c1=6.39e-7, thr30=0.0, thr31=0.0),
+                        combine_excluded_pixels=0, removal_unsure_pixels=0)
 
 
 def stage_tol(name, depth=50):
