@@ -639,6 +639,26 @@ int vps_segment_paint_ch(const uint8_t* pan_2ch, int64_t npix, int id_channel, c
 int vps_sseg_confusion(const uint8_t* gt, int Hg, int Wg, const uint8_t* pred, int Hp, int Wp, const int32_t* ytab,
                        const int32_t* xtab, int class_num, int64_t* counts, void* stream);
 
+/* STQ video evaluation (csrc/stq_ops.hip, vps_amd/stq.py): the counting pass of Segmentation and Tracking Quality
+ * (Weber et al., "STEP", 2021) for ONE frame of a video. The definition the counts follow is restated in vps_amd/stq.py.
+ *   gt_rgb, pred_rgb   DEVICE uint8 [npix][3] panoptic maps (segment id = R + 256 G + 65536 B); any byte alignment, read as aligned dwords,
+ *                      nothing outside the 3 * npix bytes of each is read
+ *   gt_ids, pred_ids   DEVICE sorted unique uint32 ids of the VIDEO's segments; gt_info, pred_info uint8 per id: bits 0-5 class index
+ *                      (>= num_classes counts as void), bit 6 thing, bit 7 crowd (ground truth only)
+ *   conf [C][C+1], gt_size [ngt], pred_size [npred+1], inter [ngt][npred]: DEVICE int64, 8-byte aligned, caller-owned. The call ADDS to
+ *                      them and never zeroes them (as vps_sseg_confusion), launches on `stream`, does not synchronise or allocate.
+ * Per pixel (G, P): cg = class of G, void (= C) when G is 0 or unlisted; cp = class of P, void when P is 0 or unlisted; a non-zero
+ * unlisted P also adds 1 to pred_size[npred]. crowd = cg thing and G crowd; gt_track = cg thing and not crowd; pred_track = cp thing and
+ * not crowd. cg != void: conf[cg][cp] += 1; gt_track: gt_size[G] += 1; pred_track: pred_size[P] += 1; both: inter[G][P] += 1.
+ * Tables of at most vps_stq_lds_cells() = 12288 cells in all (C (C+1) + ngt + npred + 1 + ngt npred) are counted in a workgroup-private
+ * LDS image and added with one 64-bit atomic per non-zero cell and workgroup; larger ones take 64-bit global atomics per run of equal
+ * pairs. Both give the same tables. Errors before any launch: -1001 null pointer, -1002 npix outside 1 .. 2^31-1, -1003 num_classes
+ * outside 1..63, -1004 negative count, -1005 more than 2^26 cells in all, -1006 a table that is not 8-byte aligned. */
+int vps_stq_accumulate(const uint8_t* gt_rgb, const uint8_t* pred_rgb, int64_t npix, const uint32_t* gt_ids, const uint8_t* gt_info, int ngt,
+                       const uint32_t* pred_ids, const uint8_t* pred_info, int npred, int num_classes, int64_t* conf, int64_t* gt_size,
+                       int64_t* pred_size, int64_t* inter, void* stream);
+int vps_stq_lds_cells(void);
+
 /* PNG output without a match search (csrc/png_ops.hip): a uint8 [H][W][C] DEVICE image, C = 1 or 3 in stored
  * order, row stride in bytes -> one zlib stream for the IDAT chunk of an 8-bit grey / RGB PNG. The format is fixed:
  *   filter   per row None (0), Sub (1) or Up (2) by the smallest sum of |int8(residual)|, a tie to the lower number; S = the rows in

@@ -69,6 +69,8 @@ def parse_args(argv=None):
     ap.add_argument('--flow-max-rad', type=float, default=None, metavar='X', help='one normaliser of the flow colours for all frames (default: each frame its own maximum)')
     ap.add_argument('--tubes', action='store_true', help='write tubes.json beside pred.json: the COCO run-length encoding, box and area of every tracked instance in '
                     'every labelled frame (vps_amd.tubes; off by default)')
+    ap.add_argument('--stq', action='store_true', help='after the VPQ step, score the same files with tools/eval_stq_device.py: stq.txt and stq-tracks.json '
+                    'beside the vpq-*.txt files (needs the ground truth; off by default)')
     ap.add_argument('--dry-run', action='store_true')
     ap.add_argument('--dry-size', default='128x256'); ap.add_argument('--dry-videos', type=int, default=1); ap.add_argument('--dry-frames', type=int, default=16)
     ap.add_argument('--check-only', action='store_true')
@@ -305,6 +307,12 @@ def run(args, tmp):
         eval_vpq_device.main(ev)
         fin = os.path.join(output_dir, 'vpq-final.txt')
         report['vpq_final'] = open(fin).read().strip().splitlines()[-3:] if os.path.exists(fin) else None
+        if args.stq:                                        # a key of its own: without the option the report is what it was
+            import eval_stq_device
+            r = eval_stq_device.main(ev + ['--device', str(dev)])
+            report['stq'] = dict(stq=round(100 * r['stq'], 4), aq=round(100 * r['aq'], 4), sq=round(100 * r['sq'], 4), tracks=r['n'],
+                                 file=os.path.join(output_dir, 'stq.txt'))
+            print('STQ %.4f  AQ %.4f  SQ %.4f' % (100 * r['stq'], 100 * r['aq'], 100 * r['sq']))
     print(json.dumps(report))
     return 0
 

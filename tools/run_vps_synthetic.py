@@ -161,7 +161,24 @@ def vpq(gt, pred, videos, nper, dev):
     return out
 
 
-def main():
+def stq(gt_dir, gt_json, pred_dir, names, out, nper, dev):
+    """tools/eval_stq_device.py on the files of this run: the ground truth (the `pan_pred/` PNGs and annotations of `gt_dir`) is laid
+    out as that tool reads it under `out`/stq_truth/; stq.txt and stq-tracks.json go beside pred.json"""
+    import shutil
+    import eval_stq_device
+    truth = os.path.join(out, 'stq_truth')
+    os.makedirs(truth, exist_ok=True)
+    images = [dict(id=n.replace('_newImg8bit.png', ''), file_name=n) for n in names]
+    for im in images:
+        shutil.copy(os.path.join(gt_dir, 'pan_pred', im['id'] + '.png'), os.path.join(truth, im['file_name'].replace('_newImg8bit.png', '_final_mask.png')))
+    gt_file = os.path.join(out, 'stq_gt.json')
+    with open(gt_file, 'w') as f:
+        json.dump(dict(annotations=gt_json['annotations'], categories=CATEGORIES, images=images), f)
+    return eval_stq_device.main(['--submit_dir', pred_dir, '--truth_dir', truth, '--pan_gt_json_file', gt_file, '--nframes_per_video', str(nper),
+                                 '--device', str(dev)])
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--videos', type=int, default=2)
     ap.add_argument('--frames', type=int, default=30)
@@ -184,7 +201,9 @@ def main():
     ap.add_argument('--flow', default=None, metavar='DIR', help='write DIR/<name>.<ext> for every frame: the FlowNet2 flow of the frame (off by default)')
     ap.add_argument('--flow-format', default='jpg', choices=['jpg', 'png', 'flo'], help='colour image (jpg, png) or the raw Middlebury field (flo)')
     ap.add_argument('--flow-max-rad', type=float, default=None, metavar='X', help='one normaliser of the flow colours for all frames (default: each frame its own maximum)')
-    args = ap.parse_args()
+    ap.add_argument('--stq', action='store_true', help='after the VPQ step, score the same files with tools/eval_stq_device.py: pred/stq.txt and '
+                    'pred/stq-tracks.json (off by default)')
+    args = ap.parse_args(argv)
     dev = torch.device('cuda:0')
     labeled_fid, lambda_ = 20, 5
     overlay = (args.overlay, args.overlay_quality, args.overlay_alpha) if args.overlay else None
@@ -212,6 +231,11 @@ def main():
                   pq_per_window={str(k): round(100 * score[k]['pq'], 4) for k in (1, 2, 3, 4)},
                   seconds=dict(model=round(dt, 3), postprocess_and_png=round(dpost, 3), eval=round(deval, 3)),
                   frames_per_s_upload_prep_model_sequential=round(args.videos * args.frames / dt, 2))
+    if args.stq:                                        # a key of its own: without the option the report is what it was
+        sys.path.insert(0, os.path.join(ROOT, 'tools'))
+        r = stq(os.path.join(args.out, 'gt' if args.gt_prec else 'pred'), gt[1], os.path.join(args.out, 'pred'), names, args.out, nper, dev)
+        report['stq'] = dict(stq=round(100 * r['stq'], 4), aq=round(100 * r['aq'], 4), sq=round(100 * r['sq'], 4), tracks=r['n'])
+        print('STQ %.4f  AQ %.4f  SQ %.4f' % (100 * r['stq'], 100 * r['aq'], 100 * r['sq']))
     if overlay_video:                                   # a key of its own: without the option the report is what it was
         report['overlay_video'] = dict(files=overlay_video['files'], sampling=args.overlay_video_sampling)
     with open(os.path.join(args.out, 'report.json'), 'w') as f:

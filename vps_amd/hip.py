@@ -36,6 +36,7 @@ SYMBOLS = [
     'vps_jpeg_scan_bound', 'vps_jpeg_encode_scan', 'vps_jpeg_wrap',
     'vps_flow_max_radius', 'vps_flow_colour',
     'vps_rle_runs', 'vps_rle_runs_ws', 'vps_rle_band_rows', 'vps_rle_strings', 'vps_rle_strings_bound',
+    'vps_stq_accumulate', 'vps_stq_lds_cells',
     'vps_y4m_info', 'vps_y4m_frame_header', 'vps_y4m_write_header', 'vps_yuv_to_bgr', 'vps_bgr_to_yuv', 'vps_yuv_tile',
 ]
 
@@ -263,6 +264,9 @@ def load():
     lib.vps_segment_stats_ch.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.vps_segment_paint_ch.argtypes = [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]
     lib.vps_sseg_confusion.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+    lib.vps_stq_accumulate.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]
+    lib.vps_stq_lds_cells.argtypes = []
     _lib = lib
     return lib
 
