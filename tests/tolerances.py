@@ -68,7 +68,35 @@ the float64 one, never below the floor (absolute figures, measured on the tests'
   MaskRemoval resized logits, n40_c2            5.38e-7                        4       -                              2.15e-6      0
   MaskRemoval resized logits, n40_c1            6.39e-7                        4       -                              2.55e-6      0
   MaskRemoval, thr30 / thr31 (all-ones masks)   0                              4       -                              0            0
-  (the single-box test of tests/test_hip_ops.py allows 7e-6 max|m28| = about 5e-5 around zero: twenty times these)"""
+  (the single-box test of tests/test_hip_ops.py allows 7e-6 max|m28| = about 5e-5 around zero: twenty times these)
+
+Kernel-level tests of the neck and flow glue kernels (tests/test_nn_ops_gpu.py against tests/nn_restate.py, cases in tests/nn_cases.py):
+nearest resize, max pool, BFP scatter / scatter_all, the transposes, axpb (one fma) and flow_warp's all-outside zeros compare BITWISE.
+Every other case compares with the float64 restatement under bound = max(floor, 4 x max|float32 restatement - float64 restatement|),
+floor = one float32 ulp of the case's largest |reference|, DERIVED by the test from its inputs and asserted on the CPU
+(tests/test_nn_restate.py) not to exceed the cap = what tests/test_hip_ops.py allows the kernel, atol + rtol max|reference|. Largest figures
+per kernel over its bounded cases (absolute; per case in NN_OPS_MEASURED below as (float32 vs float64, bound used, measured max error of the
+kernel on an MI355X)):
+
+  kernel          cases  f32 v f64  floor    bound     kernel    cap
+  resize            18   4.54e-06 3.81e-06 1.82e-05  4.18e-06  1e-06 + 1e-06 |ref|
+  pool              24   3.44e-07 2.38e-07 1.38e-06  3.44e-07  1e-06 + 1e-06 |ref|
+  gather             5   1.61e-07 4.77e-07 6.44e-07  1.61e-07  1e-06 + 1e-06 |ref|
+  groupnorm         30   2.76e-06 4.77e-07 1.11e-05  5.13e-07  1e-05 + 1e-05 |ref|
+  groupnorm          1   12.1     4.77e-07 48.4      3.74e-05  (ill-conditioned by design: relu_C64_G32_p560_relu1_ldv_far_mean)
+  groupnorm          1   9.46     4.77e-07 37.8      3.89e-05  (ill-conditioned by design: relu_C2_G1_p560_relu0_ld+4s_far_mean)
+  tcea_temporal     12   3.46e-07 2.38e-07 1.38e-06  3.49e-07  1e-05 + 1e-05 |ref|
+  tcea_temporal      1   5.95e-06 2.38e-07 2.38e-05  5.95e-06  (ill-conditioned by design: C64_p67_saturated)
+  tcea_modulate      3   6.03e-07 4.77e-07 2.41e-06  6.03e-07  1e-06 + 1e-06 |ref|
+  resample2d        27   2.83e-07 2.38e-07 1.13e-06  2.38e-07  1e-06 + 1e-06 |ref|
+  channelnorm       12   3.85e-07 4.77e-07 1.54e-06  3.85e-07  1e-07 + 1e-06 |ref|
+  flow_warp         12   1.36e-05 2.38e-07 5.45e-05  1.36e-05  0.0001 + 0.0001 |ref|
+  flow_stage        20   2.12e-06 9.54e-07 8.49e-06  2.11e-06  1e-05 + 1e-05 |ref|
+  flow_stage_full    4   3.54e-07 4.77e-07 1.42e-06  2.64e-07  1e-05 + 1e-05 |ref|
+  flow_prep         18   6.05e-06 7.63e-06 2.42e-05  3.53e-06  1e-05 + 0 |ref|
+  (resize: the large figures belong to alpha = -20, |reference| up to 80; flow_prep: to rgb_mean, values of ~100, cap 1e-4. The two far-mean
+  GroupNorm cases are also held to the bound of tests/nn_cases.py groupnorm_affine_bound, 1.9e-2 / 1.4e-2, derived from the number
+  formats: measured 3.7e-5 / 3.9e-5; float32 statistics would be off by whole units.)"""
 
 STAGE = dict(flow=5e-5, fpn=5e-5, neck=2e-3, fcn_score=2e-3, cls_score=2e-3, bbox_pred=2e-3, score=2e-3)
 STAGE_R101 = dict(neck=1e-2, fcn_score=1e-2, cls_score=1e-2, bbox_pred=1e-2, score=1e-2)      # the stages behind the FPN of the 101-layer model
@@ -84,6 +112,124 @@ HEAD_OPS_MEASURED = dict(softmax_f32_vs_f64=1.6e-7, log_softmax_f32_vs_f64=3.8e-
 PAN_OPS_MEASURED = dict(combine_f32_vs_f64=dict(k5=1.28e-6, up2_k70=9.07e-7, up1_k3=3.73e-8, up8_k12=8.79e-7, k244=1.30e-6, c33_k12=1.10e-6, s7_k12=1.02e-6),
                         removal_resized_f32_vs_f64=dict(n1=9.69e-8, n12_c3=6.72e-7, n40_c2=5.38e-7, n40_c1=6.39e-7, thr30=0.0, thr31=0.0),
                         combine_excluded_pixels=0, removal_unsure_pixels=0)
+
+# the same record for tests/test_nn_ops_gpu.py, per kernel and case: (max|float32 - float64 restatement|, bound used, max error the kernel showed)
+NN_OPS_MEASURED = {
+    'resize': {
+        'bilinear_7x5_12x9_c8w_a1': (2.41e-07, 9.65e-07, 2.57e-07), 'bilinear_7x5_12x9_c8s_a0.25': (4.56e-08, 1.82e-07, 5.3e-08),
+        'bilinear_7x5_12x9_c3_a-20': (3.93e-06, 1.57e-05, 4.18e-06), 'bilinear_33x17_17x9_c8w_a1': (1.92e-07, 7.68e-07, 1.9e-07),
+        'bilinear_33x17_17x9_c8s_a0.25': (6.54e-08, 2.62e-07, 5.95e-08), 'bilinear_33x17_17x9_c3_a-20': (3.68e-06, 1.47e-05, 3.58e-06),
+        'bilinear_5x9_13x4_c8w_a1': (2.58e-07, 1.03e-06, 1.91e-07), 'bilinear_5x9_13x4_c8s_a0.25': (3.82e-08, 1.53e-07, 3.85e-08),
+        'bilinear_5x9_13x4_c3_a-20': (4.54e-06, 1.82e-05, 3.11e-06), 'bilinear_1x6_3x11_c8w_a1': (1.75e-07, 6.99e-07, 8.19e-08),
+        'bilinear_1x6_3x11_c8s_a0.25': (3.99e-08, 1.6e-07, 2.61e-08), 'bilinear_1x6_3x11_c3_a-20': (3.33e-06, 1.33e-05, 1.94e-06),
+        'bilinear_6x1_4x1_c8w_a1': (5.96e-08, 2.38e-07, 5.96e-08), 'bilinear_6x1_4x1_c8s_a0.25': (2.24e-08, 8.94e-08, 1.86e-08),
+        'bilinear_6x1_4x1_c3_a-20': (1.67e-06, 6.68e-06, 1.67e-06), 'bilinear_8x12_8x12_c8w_a1': (0, 2.38e-07, 0),
+        'bilinear_8x12_8x12_c8s_a0.25': (0, 5.96e-08, 0), 'bilinear_8x12_8x12_c3_a-20': (1.91e-06, 7.63e-06, 1.91e-06),
+    },
+    'pool': {
+        'avg_1x1_c4w_normal': (3.31e-09, 1.49e-08, 3.31e-09), 'avg_1x1_c4w_negative': (1.32e-08, 5.3e-08, 1.32e-08),
+        'avg_1x1_c3_normal': (3.31e-09, 1.49e-08, 3.31e-09), 'avg_1x1_c3_negative': (9.93e-09, 3.97e-08, 9.93e-09),
+        'avg_1x7_c4w_normal': (2.98e-08, 1.19e-07, 2.98e-08), 'avg_1x7_c4w_negative': (5.3e-08, 2.12e-07, 5.3e-08),
+        'avg_1x7_c3_normal': (2.32e-08, 9.27e-08, 2.32e-08), 'avg_1x7_c3_negative': (5.96e-08, 2.38e-07, 5.96e-08),
+        'avg_2x2_c4w_normal': (2.32e-08, 9.27e-08, 2.32e-08), 'avg_2x2_c4w_negative': (4.64e-08, 1.85e-07, 4.64e-08),
+        'avg_2x2_c3_normal': (3.31e-08, 1.32e-07, 3.31e-08), 'avg_2x2_c3_negative': (5.3e-08, 2.12e-07, 5.3e-08),
+        'avg_2x9_c4w_normal': (2.65e-08, 1.06e-07, 2.65e-08), 'avg_2x9_c4w_negative': (1.06e-07, 4.24e-07, 1.06e-07),
+        'avg_2x9_c3_normal': (5.13e-08, 2.05e-07, 5.13e-08), 'avg_2x9_c3_negative': (1.59e-07, 6.36e-07, 1.59e-07),
+        'avg_9x2_c4w_normal': (3.64e-08, 1.46e-07, 3.64e-08), 'avg_9x2_c4w_negative': (1.32e-07, 5.3e-07, 1.32e-07),
+        'avg_9x2_c3_normal': (3.64e-08, 1.46e-07, 3.64e-08), 'avg_9x2_c3_negative': (1.19e-07, 4.77e-07, 1.19e-07),
+        'avg_17x9_c4w_normal': (7.95e-08, 3.18e-07, 7.95e-08), 'avg_17x9_c4w_negative': (3.44e-07, 1.38e-06, 3.44e-07),
+        'avg_17x9_c3_normal': (8.32e-08, 3.33e-07, 8.32e-08), 'avg_17x9_c3_negative': (2.78e-07, 1.11e-06, 2.78e-07),
+    },
+    'gather': {
+        'L1': (0, 4.77e-07, 0), 'L2': (1.19e-07, 4.77e-07, 1.19e-07), 'L3': (1.59e-07, 6.36e-07, 1.59e-07), 'L5': (1.61e-07, 6.44e-07, 1.61e-07),
+        'r1_3': (1.19e-07, 4.77e-07, 1.19e-07),
+    },
+    'groupnorm': {
+        'relu_C256_G32_p37_relu0_ldv_normal': (6.68e-07, 2.67e-06, 4.26e-07), 'relu_C64_G32_p37_relu1_ldv_normal': (6.46e-07, 2.58e-06, 3.56e-07),
+        'relu_C32_G32_p37_relu0_ld+4v_normal': (6.69e-07, 2.68e-06, 3.78e-07), 'relu_C16_G4_p37_relu1_ld+4v_normal': (4.88e-07, 1.95e-06, 2.73e-07),
+        'relu_C8_G8_p37_relu0_lds_normal': (4.53e-07, 1.81e-06, 3.08e-07), 'relu_C4_G1_p37_relu1_lds_normal': (2.71e-07, 1.08e-06, 1.52e-07),
+        'relu_C4_G4_p37_relu0_ld+4s_normal': (2.61e-07, 1.04e-06, 2.87e-07), 'relu_C2_G1_p37_relu1_ld+4s_normal': (1.57e-07, 6.29e-07, 2.48e-07),
+        'relu_C1_G1_p37_relu0_lds_normal': (4.2e-07, 1.68e-06, 2.46e-07), 'relu_C128_G1_p37_relu1_ldv_normal': (4.29e-07, 1.71e-06, 5.13e-07),
+        'relu_C64_G32_p1_relu1_ldv_normal': (2.76e-06, 1.11e-05, 2.09e-07), 'relu_C2_G1_p1_relu0_ld+4s_normal': (2.49e-08, 1.19e-07, 2.49e-08),
+        'relu_C64_G32_p3_relu0_ld+4s_normal': (6.57e-07, 2.63e-06, 2.52e-07), 'relu_C2_G1_p3_relu1_lds_normal': (1.38e-07, 5.52e-07, 1.88e-08),
+        'relu_C64_G32_p560_relu1_ldv_normal': (1.47e-06, 5.86e-06, 4.62e-07), 'relu_C2_G1_p560_relu0_ld+4s_normal': (6.85e-07, 2.74e-06, 2.99e-07),
+        'relu_C64_G32_p37_relu1_ld+4v_normal': (6.63e-07, 2.65e-06, 4.07e-07), 'relu_C64_G32_p37_relu0_lds_normal': (4.74e-07, 1.9e-06, 3.25e-07),
+        'relu_C2_G1_p37_relu0_lds_normal': (1.29e-07, 5.15e-07, 1.1e-07), 'relu_C64_G32_p37_relu1_ldv_constant': (0, 5.96e-08, 0),
+        'relu_C16_G4_p3_relu0_ld+4s_constant': (0, 2.98e-08, 0), 'relu_C2_G1_p37_relu0_lds_constant': (0, 5.96e-08, 0),
+        'relu_C64_G32_p560_relu1_ldv_far_mean': (12.1, 48.4, 3.74e-05), 'relu_C2_G1_p560_relu0_ld+4s_far_mean': (9.46, 37.8, 3.89e-05),
+        'apply_C16_G4_p37_relu0_ldv_normal_rep1': (4.67e-07, 1.87e-06, 3.95e-07),
+        'apply_C16_G4_p37_relu1_ldv_normal_rep1': (4.21e-07, 1.68e-06, 3.06e-07),
+        'apply_C16_G4_p37_relu0_lds_normal_rep1': (4.78e-07, 1.91e-06, 2.55e-07),
+        'apply_C16_G4_p37_relu1_lds_normal_rep1': (3.02e-07, 1.21e-06, 2.62e-07),
+        'apply_C16_G4_p37_relu0_ld+4v_normal_rep3': (4.21e-07, 1.68e-06, 5.02e-07),
+        'apply_C16_G4_p37_relu1_ld+4v_normal_rep3': (3.57e-07, 1.43e-06, 3.57e-07),
+        'apply_C16_G4_p37_relu0_ld+4s_normal_rep3': (3.37e-07, 1.35e-06, 4.64e-07),
+        'apply_C16_G4_p37_relu1_ld+4s_normal_rep3': (3.15e-07, 1.26e-06, 3.13e-07),
+    },
+    'tcea_temporal': {
+        'C4_p1': (4.04e-08, 1.62e-07, 4.04e-08), 'C4_p5': (1.15e-07, 4.6e-07, 8.42e-08), 'C4_p67': (1.29e-07, 5.15e-07, 1.12e-07),
+        'C64_p1': (8.73e-08, 3.49e-07, 2.77e-08), 'C64_p5': (2.22e-07, 8.87e-07, 1.06e-07), 'C64_p67': (1.92e-07, 7.66e-07, 1.89e-07),
+        'C256_p1': (6.78e-08, 2.71e-07, 9.9e-08), 'C256_p5': (1.83e-07, 7.32e-07, 1.95e-07), 'C256_p67': (2.87e-07, 1.15e-06, 2.87e-07),
+        'C512_p1': (2.03e-07, 8.12e-07, 2.03e-07), 'C512_p5': (2.64e-07, 1.06e-06, 2.64e-07), 'C512_p67': (3.46e-07, 1.38e-06, 3.49e-07),
+        'C64_p67_saturated': (5.95e-06, 2.38e-05, 5.95e-06),
+    },
+    'tcea_modulate': {
+        'flat_n1': (0, 1.49e-08, 0), 'flat_n1027': (6.03e-07, 2.41e-06, 6.03e-07), 'ld_C8_p37': (4.78e-07, 1.91e-06, 4.78e-07),
+    },
+    'resample2d': {
+        'C1_normal_ccc': (2.83e-07, 1.13e-06, 1.2e-07), 'C1_normal_hhh': (1.35e-07, 5.4e-07, 2.38e-07),
+        'C1_normal_hch': (1.44e-07, 5.77e-07, 1.77e-07), 'C1_integer_ccc': (0, 2.38e-07, 0), 'C1_integer_hhh': (0, 2.38e-07, 0),
+        'C1_integer_hch': (0, 2.38e-07, 0), 'C1_edges_ccc': (4.47e-08, 2.38e-07, 4.47e-08), 'C1_edges_hhh': (8.94e-08, 3.58e-07, 8.94e-08),
+        'C1_edges_hch': (2.98e-08, 1.19e-07, 2.98e-08), 'C3_normal_ccc': (2.1e-07, 8.4e-07, 1.79e-07), 'C3_normal_hhh': (1.86e-07, 7.43e-07, 2.01e-07),
+        'C3_normal_hch': (1.97e-07, 7.86e-07, 1.6e-07), 'C3_integer_ccc': (0, 2.38e-07, 0), 'C3_integer_hhh': (0, 2.38e-07, 0),
+        'C3_integer_hch': (0, 2.38e-07, 0), 'C3_edges_ccc': (5.96e-08, 2.38e-07, 5.96e-08), 'C3_edges_hhh': (7.82e-08, 3.13e-07, 7.82e-08),
+        'C3_edges_hch': (5.96e-08, 2.38e-07, 5.96e-08), 'C5_normal_ccc': (2.65e-07, 1.06e-06, 2.04e-07),
+        'C5_normal_hhh': (2.38e-07, 9.54e-07, 2.05e-07), 'C5_normal_hch': (2.38e-07, 9.5e-07, 2.38e-07), 'C5_integer_ccc': (0, 2.38e-07, 0),
+        'C5_integer_hhh': (0, 2.38e-07, 0), 'C5_integer_hch': (0, 2.38e-07, 0), 'C5_edges_ccc': (1.19e-07, 4.77e-07, 1.19e-07),
+        'C5_edges_hhh': (5.96e-08, 2.38e-07, 5.96e-08), 'C5_edges_hch': (5.96e-08, 2.38e-07, 5.96e-08),
+    },
+    'channelnorm': {
+        'C1_cc': (0, 2.38e-07, 0), 'C1_hh': (0, 2.38e-07, 0), 'C1_hc': (0, 2.38e-07, 0), 'C1_ch': (0, 2.38e-07, 0),
+        'C3_cc': (1.73e-07, 6.92e-07, 1.72e-07), 'C3_hh': (1.53e-07, 6.11e-07, 1.53e-07), 'C3_hc': (2.25e-07, 8.99e-07, 1.61e-07),
+        'C3_ch': (1.88e-07, 7.51e-07, 1.55e-07), 'C5_cc': (3.85e-07, 1.54e-06, 3.85e-07), 'C5_hh': (2.67e-07, 1.07e-06, 3.77e-07),
+        'C5_hc': (2.64e-07, 1.06e-06, 2.64e-07), 'C5_ch': (2.33e-07, 9.33e-07, 2.33e-07),
+    },
+    'flow_warp': {
+        '2x9x7x8_normal': (2.22e-06, 8.87e-06, 1.08e-06), '2x9x7x8_zero': (9.36e-07, 3.75e-06, 1.06e-06),
+        '2x9x7x8_edge': (9.47e-07, 3.79e-06, 9.47e-07), '1x24x40x64_normal': (1.36e-05, 5.45e-05, 1.36e-05),
+        '1x24x40x64_zero': (1.22e-05, 4.89e-05, 1.22e-05), '1x24x40x64_edge': (9.38e-06, 3.75e-05, 8.07e-06),
+        '1x2x2x4_normal': (1.36e-07, 5.45e-07, 1.36e-07), '1x2x2x4_zero': (0, 5.96e-08, 0), '1x2x2x4_edge': (1.58e-07, 6.33e-07, 1.58e-07),
+        '2x5x16x12_normal': (2.84e-06, 1.14e-05, 2.6e-06), '2x5x16x12_zero': (2.88e-06, 1.15e-05, 2.91e-06),
+        '2x5x16x12_edge': (4.01e-06, 1.6e-05, 4.01e-06),
+    },
+    'flow_stage': {
+        '4x4_up0_div0_all_x6_od0:img': (0, 5.96e-08, 0), '4x4_up0_div0_all_x6_od0:flow': (3.73e-09, 1.19e-07, 0),
+        '4x4_up0_div0_all_x6_od0:warp': (1.99e-08, 7.96e-08, 1.96e-08), '4x4_up0_div0_all_x6_od0:diffnorm': (7.62e-08, 3.05e-07, 7.62e-08),
+        '4x4_up0_div0_all_x6_od0:flownorm': (4.53e-08, 1.81e-07, 4.53e-08), '4x4_up0_div1_flow_x6_od20:flow': (7.45e-10, 3.73e-09, 7.45e-10),
+        '4x4_up1_div0_warp_x8_od0:warp': (1.31e-08, 5.24e-08, 1.24e-08), '4x4_up1_div1_diffnorm_x8_od20:diffnorm': (3.89e-08, 1.56e-07, 5.04e-08),
+        '8x12_up0_div0_flownorm_x6_od0:flownorm': (8.33e-07, 3.33e-06, 6.92e-07), '8x12_up0_div1_img_x6_od20:img': (0, 5.96e-08, 0),
+        '8x12_up1_div0_all_x8_od0:img': (0, 5.96e-08, 0), '8x12_up1_div0_all_x8_od0:flow': (1.19e-07, 4.77e-07, 1.19e-07),
+        '8x12_up1_div0_all_x8_od0:warp': (5.96e-08, 2.38e-07, 5.96e-08), '8x12_up1_div0_all_x8_od0:diffnorm': (8.88e-08, 3.55e-07, 8.88e-08),
+        '8x12_up1_div0_all_x8_od0:flownorm': (9.53e-08, 4.77e-07, 1.89e-07), '8x12_up1_div1_flow_x8_od20:flow': (9.54e-09, 3.81e-08, 9.54e-09),
+        '20x36_up0_div0_warp_x6_od0:warp': (2.11e-06, 8.44e-06, 2.11e-06), '20x36_up0_div1_diffnorm_x6_od20:diffnorm': (2.12e-06, 8.49e-06, 2.11e-06),
+        '20x36_up1_div0_flownorm_x8_od0:flownorm': (8.97e-07, 3.59e-06, 7e-07), '20x36_up1_div1_img_x8_od20:img': (0, 5.96e-08, 0),
+    },
+    'flow_stage_full': {
+        'mode0_4x4': (6.03e-08, 2.41e-07, 6.03e-08), 'mode0_8x12': (3.54e-07, 1.42e-06, 2.64e-07), 'mode1_4x4': (1.45e-07, 5.81e-07, 1.45e-07),
+        'mode1_8x12': (1.91e-07, 7.63e-07, 1.91e-07),
+    },
+    'flow_prep': {
+        '5x7_5x7_nblk1_ld8': (6.31e-08, 2.52e-07, 6.9e-08), '5x7_5x7_nblk1_ld8:rgb_mean': (4.46e-06, 1.78e-05, 3.17e-06),
+        '5x7_5x7_nblk4_ld12': (7.9e-08, 3.16e-07, 4.87e-08), '5x7_5x7_nblk4_ld12:rgb_mean': (6.05e-06, 2.42e-05, 3.53e-06),
+        '5x7_5x7_nblk64_ld8': (6.76e-08, 2.7e-07, 4.21e-08), '5x7_5x7_nblk64_ld8:rgb_mean': (5.14e-06, 2.06e-05, 2.73e-06),
+        '5x7_8x16_nblk1_ld12': (7.17e-08, 2.87e-07, 7.47e-08), '5x7_8x16_nblk1_ld12:rgb_mean': (2.03e-06, 8.12e-06, 1.78e-06),
+        '5x7_8x16_nblk4_ld8': (7.8e-08, 3.12e-07, 6.6e-08), '5x7_8x16_nblk4_ld8:rgb_mean': (2.05e-06, 8.21e-06, 6.83e-07),
+        '5x7_8x16_nblk64_ld12': (5.62e-08, 2.25e-07, 5.62e-08), '5x7_8x16_nblk64_ld12:rgb_mean': (1.29e-06, 5.17e-06, 1.29e-06),
+        '16x16_64x64_nblk1_ld8': (1.19e-07, 4.77e-07, 1.19e-07), '16x16_64x64_nblk1_ld8:rgb_mean': (4.83e-07, 1.93e-06, 5.98e-08),
+        '16x16_64x64_nblk4_ld12': (9.99e-08, 3.99e-07, 9.99e-08), '16x16_64x64_nblk4_ld12:rgb_mean': (1.91e-07, 9.54e-07, 1.91e-07),
+        '16x16_64x64_nblk64_ld8': (1.26e-07, 5.05e-07, 1.01e-07), '16x16_64x64_nblk64_ld8:rgb_mean': (2.79e-07, 1.12e-06, 2.79e-07),
+    },
+}
 
 
 def stage_tol(name, depth=50):

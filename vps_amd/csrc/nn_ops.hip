@@ -280,8 +280,11 @@ void groupnorm_apply_kernel(const float* __restrict__ in, int in_ld, float* __re
         if (var < 0.0) var = 0.0;
         const float rstd = (float)(1.0 / sqrt(var + (double)eps));
         const float sc = rstd * gamma[c];
-        const float bi = -sc * (float)mean + beta[c];
-        float v = in[(size_t)pix * in_ld + c] * sc + bi;
+        // (x - mean) * sc + beta with the mean split into a float and its remainder: a folded shift -sc * mean + beta is rounded at the
+        // magnitude of sc * |mean| and loses the output where |mean| >> std (a constant 3.25 came out 5e-5 off beta)
+        const float mh = (float)mean;
+        const float bi = (float)((double)beta[c] - (double)sc * (mean - (double)mh));
+        float v = (in[(size_t)pix * in_ld + c] - mh) * sc + bi;
         if (relu) v = v > 0.f ? v : 0.f;
         out[(size_t)pix * out_ld + out_coff + c] = v;
     }
@@ -327,7 +330,7 @@ void groupnorm_apply4_kernel(const float* __restrict__ in, int in_ld, float* __r
                              int relu, const double* __restrict__ stats_g, int nrep) {
     // the sums may come as nrep partial copies (conv epilogue): add them up once per block
     __shared__ double stats[512];
-    __shared__ float sc_t[256], bi_t[256];
+    __shared__ float sc_t[256], bi_t[256], mh_t[256];
     for (int i = threadIdx.x; i < 2 * G; i += blockDim.x) {
         double a = 0.0;
         for (int r = 0; r < nrep; ++r) a += stats_g[(size_t)r * 2 * G + i];
@@ -339,7 +342,7 @@ void groupnorm_apply4_kernel(const float* __restrict__ in, int in_ld, float* __r
     const int cpg = C / G;
     const double cnt = (double)npix * cpg;
     // per-channel scale / shift ONCE per block (C <= 256 entries): the fp64 divide + square root per ELEMENT made this pass 2x slower
-    // than the memory system (125 us for 268 MB at 256x512x256; round 5). Same expressions in the same precisions: bit-identical output.
+    // than the memory system (125 us for 268 MB at 256x512x256; round 5). Same expressions in the same precisions as the scalar kernel: bit-identical output.
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         const int g = c / cpg;
         const double mean = stats[2 * g] / cnt;
@@ -347,8 +350,10 @@ void groupnorm_apply4_kernel(const float* __restrict__ in, int in_ld, float* __r
         if (var < 0.0) var = 0.0;
         const float rstd = (float)(1.0 / sqrt(var + (double)eps));
         const float sc = rstd * gamma[c];
-        const float bi = -sc * (float)mean + beta[c];
-        sc_t[c] = sc; bi_t[c] = bi;
+        // (x - mean) * sc + beta, the mean split into a float and its remainder (see groupnorm_apply_kernel)
+        const float mh = (float)mean;
+        const float bi = (float)((double)beta[c] - (double)sc * (mean - (double)mh));
+        sc_t[c] = sc; bi_t[c] = bi; mh_t[c] = mh;
     }
     __syncthreads();
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
@@ -359,7 +364,7 @@ void groupnorm_apply4_kernel(const float* __restrict__ in, int in_ld, float* __r
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float sc = sc_t[c + e], bi = bi_t[c + e];
-            float v = x[e] * sc + bi;
+            float v = (x[e] - mh_t[c + e]) * sc + bi;
             if (relu) v = v > 0.f ? v : 0.f;
             y[e] = v;
         }
