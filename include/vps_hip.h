@@ -659,6 +659,27 @@ int vps_stq_accumulate(const uint8_t* gt_rgb, const uint8_t* pred_rgb, int64_t n
                        int64_t* pred_size, int64_t* inter, void* stream);
 int vps_stq_lds_cells(void);
 
+/* Boundary PQ / boundary VPQ (csrc/boundary_ops.hip, vps_amd/boundary.py): the boundary band of EVERY segment of a
+ * panoptic map in one call, the device form of Boundary IoU's mask_to_boundary (Cheng et al., CVPR 2021) applied per segment.
+ *   pan_rgb   DEVICE uint8 [H][W][3] panoptic map (segment id = R + 256 G + 65536 B, the maps vps_pair_count reads); any byte alignment,
+ *             nothing outside its 3 * H * W bytes is read
+ *   out_rgb   DEVICE uint8 [H][W][3], every byte written. For a pixel of id s: s == 0 (VOID) -> 0. Otherwise the pixel is INTERIOR when
+ *             the whole (2d+1) x (2d+1) window centred on it lies inside the image and every pixel of the window has id s; an interior
+ *             pixel -> 0xFFFFFF (the reserved fill id), every other pixel is a band pixel -> s. (Padding the mask with a ring of zeros
+ *             and eroding it d times with a 3 x 3 kernel removes exactly the pixels that are not interior.)
+ *   ws        DEVICE workspace, 4-byte aligned, at least vps_boundary_band_ws(H, W, d) = 4 * H * W bytes: one dword per pixel, the id and
+ *             the flag "the row window [x-d, x+d] is inside the image and uniform"
+ * Two launches on `stream` (row pass, column pass), no sync, no allocation, no atomics; the bytes do not depend on the launch geometry
+ * or on the workspace's size. The work per pixel does not grow with d: the row pass takes a prefix sum of the id changes over
+ * 512 columns plus a halo of d, the column pass walks 32 rows plus a halo of d per lane and keeps the last row that changed.
+ * vps_boundary_tile (HOST): rows_cols[0] = rows of a column-pass tile, rows_cols[1] = columns of a row-pass tile (constants of the build,
+ * for tests that put edges on the seams).
+ * Errors before any launch: -1001 null pointer, -1002 H or W < 1 or H * W >= 2^31, -1003 d outside 1..255, -1004 workspace too small
+ * or not 4-byte aligned. */
+int vps_boundary_band(const uint8_t* pan_rgb, int H, int W, int d, uint8_t* out_rgb, void* ws, int64_t ws_bytes, void* stream);
+int vps_boundary_band_ws(int H, int W, int d, int64_t* ws_bytes);
+int vps_boundary_tile(int32_t* rows_cols);
+
 /* PNG output without a match search (csrc/png_ops.hip): a uint8 [H][W][C] DEVICE image, C = 1 or 3 in stored
  * order, row stride in bytes -> one zlib stream for the IDAT chunk of an 8-bit grey / RGB PNG. The format is fixed:
  *   filter   per row None (0), Sub (1) or Up (2) by the smallest sum of |int8(residual)|, a tie to the lower number; S = the rows in

@@ -28,6 +28,9 @@ def parse_args(argv=None):
     ap.add_argument('--pan_gt_json_file', type=str, default='data/cityscapes_vps/panpotic_gt_val_city_vps.json', help='ground truth json')
     ap.add_argument('--nframes_per_video', type=int, default=6)
     ap.add_argument('--device', type=str, default='cuda')
+    # the command line of tools/eval_vpq_device.py is taken whole: its boundary options are accepted and ignored (STQ has no boundary form)
+    ap.add_argument('--boundary', action='store_true', help='accepted for tools/eval_vpq_device.py\'s command line; no effect here')
+    ap.add_argument('--boundary-ratio', type=float, default=0.02, help='accepted for tools/eval_vpq_device.py\'s command line; no effect here')
     return ap.parse_args(argv)
 
 

@@ -28,6 +28,8 @@ def parse_args(argv=None):
     ap.add_argument('--pan_gt_json_file', type=str, default='data/cityscapes_vps/panpotic_gt_val_city_vps.json', help='ground truth json')
     ap.add_argument('--nframes_per_video', type=int, default=6)
     ap.add_argument('--device', type=str, default='cuda')
+    ap.add_argument('--boundary', action='store_true', help='also write bvpq-<k>.txt and bvpq-final.txt: boundary VPQ (vps_amd.boundary; off by default)')
+    ap.add_argument('--boundary-ratio', type=float, default=0.02, help='--boundary: width of the band as a fraction of the image diagonal')
     return ap.parse_args(argv)
 
 
@@ -92,8 +94,15 @@ def main(argv=None):
         f.write('vpq_all:%.4f\n' % (sum(vpq['All']) / 4))
         f.write('vpq_thing:%.4f\n' % (sum(vpq['Things']) / 4))
         f.write('vpq_stuff:%.4f\n' % (sum(vpq['Stuff']) / 4))
+    out = {n: sum(v) / 4 for n, v in vpq.items()}
+    if args.boundary:                            # files of their own beside the vpq-* ones, which are what they are without the option
+        from vps_amd import boundary
+        t0 = time.time()
+        b = boundary.bvpq_compute(videos, categories, output_dir, device=args.device, boundary_ratio=args.boundary_ratio)
+        out['boundary'] = {n: b[n] for n in ('All', 'Things', 'Stuff')}
+        print('==> boundary vpq_stat: %.2f sec  %s' % (time.time() - t0, [round(b[n], 4) for n in ('All', 'Things', 'Stuff')]))
     print('==> All: %.2f sec' % (time.time() - t_all))
-    return {n: sum(v) / 4 for n, v in vpq.items()}
+    return out
 
 
 if __name__ == '__main__':

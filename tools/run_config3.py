@@ -71,6 +71,9 @@ def parse_args(argv=None):
                     'every labelled frame (vps_amd.tubes; off by default)')
     ap.add_argument('--stq', action='store_true', help='after the VPQ step, score the same files with tools/eval_stq_device.py: stq.txt and stq-tracks.json '
                     'beside the vpq-*.txt files (needs the ground truth; off by default)')
+    ap.add_argument('--boundary', action='store_true', help='with the VPQ step: also write bvpq-<k>.txt and bvpq-final.txt, boundary VPQ (vps_amd.boundary; needs '
+                    'the ground truth; off by default)')
+    ap.add_argument('--boundary-ratio', type=float, default=0.02, help='--boundary: width of the band as a fraction of the image diagonal')
     ap.add_argument('--dry-run', action='store_true')
     ap.add_argument('--dry-size', default='128x256'); ap.add_argument('--dry-videos', type=int, default=1); ap.add_argument('--dry-frames', type=int, default=16)
     ap.add_argument('--check-only', action='store_true')
@@ -304,9 +307,11 @@ def run(args, tmp):
         ev = ['--submit_dir', output_dir, '--truth_dir', truth_dir, '--pan_gt_json_file', gt_json or os.path.join(args.data_root, 'panoptic_gt_%s_city_vps.json' % args.mode)]
         if args.dry_run:
             ev += ['--nframes_per_video', str(len(names) // max(args.n_video, 1))]
-        eval_vpq_device.main(ev)
+        eval_vpq_device.main(ev + (['--boundary', '--boundary-ratio', str(args.boundary_ratio)] if args.boundary else []))
         fin = os.path.join(output_dir, 'vpq-final.txt')
         report['vpq_final'] = open(fin).read().strip().splitlines()[-3:] if os.path.exists(fin) else None
+        if args.boundary:                                   # a key of its own: without the option the report is what it was
+            report['bvpq_final'] = open(os.path.join(output_dir, 'bvpq-final.txt')).read().strip().splitlines()[-3:]
         if args.stq:                                        # a key of its own: without the option the report is what it was
             import eval_stq_device
             r = eval_stq_device.main(ev + ['--device', str(dev)])

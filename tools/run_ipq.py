@@ -38,6 +38,8 @@ def parse_args(argv=None):
     ap.add_argument('--prec', default='f16x3', choices=['f32', 'bf16x6', 'f16x3'])
     ap.add_argument('--tubes', action='store_true', help='write <out>_pans_unified/tubes.json: the COCO run-length encoding, box and area of every instance of every '
                     'image (vps_amd.tubes; one "video" of one frame per image; off by default)')
+    ap.add_argument('--boundary', action='store_true', help='also write <out>_pans_unified/bpq.txt: boundary PQ (vps_amd.boundary; off by default)')
+    ap.add_argument('--boundary-ratio', type=float, default=0.02, help='--boundary: width of the band as a fraction of the image diagonal')
     ap.add_argument('--dry-run', action='store_true')
     ap.add_argument('--height', type=int, default=128); ap.add_argument('--width', type=int, default=256)
     ap.add_argument('--dry-images', type=int, default=3)
@@ -161,6 +163,13 @@ def run(args, tmp):
     pred_pans_2ch = [two[k] for k in sorted(two)]
     ipq.evaluate_panoptic(pred_pans_2ch, args.out.replace('.pkl', '_pans_unified'), gt_file, os.path.join(args.data_root, 'panoptic'),
                           None, color_generator(categories), device=dev)
+    if args.boundary:                       # from the files evaluate_panoptic has just written: gt.json, pred.json and pan/
+        from vps_amd import boundary
+        out_dir = args.out.replace('.pkl', '_pans_unified')
+        gt_all, pred_all = json.load(open(os.path.join(out_dir, 'gt.json'))), json.load(open(os.path.join(out_dir, 'pred.json')))
+        gt_pans = [np.array(Image.open(os.path.join(args.data_root, 'panoptic', item['file_name']))) for item in gt_all['images']]
+        pred_pans = [np.array(Image.open(ipq.ipq_png_name(os.path.join(out_dir, 'pan'), item['file_name']))) for item in gt_all['images']]
+        boundary.bpq_compute(gt_all, pred_all, gt_pans, pred_pans, categories, out_dir, device=dev, boundary_ratio=args.boundary_ratio)
     if args.tubes:
         from vps_amd.tubes import TubeCollector
         col = TubeCollector(things_only=True, id_channel=1, device=dev)       # image-level maps: the instance id is pan_ins, 0 for stuff

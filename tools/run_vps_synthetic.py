@@ -178,7 +178,18 @@ def stq(gt_dir, gt_json, pred_dir, names, out, nper, dev):
                                  '--device', str(dev)])
 
 
-def main(argv=None):
+def bvpq(gt, pred, videos, nper, dev, out_dir, ratio):
+    """boundary VPQ of the same clips (vps_amd.boundary): bvpq-<k>.txt and bvpq-final.txt go beside pred.json"""
+    from vps_amd import boundary
+    cats = {c['id']: c for c in CATEGORIES}
+    clips = []
+    for v in range(videos):
+        sl = slice(v * nper, (v + 1) * nper)
+        clips.append([(g, p, gp, pp, {}) for g, p, gp, pp in zip(gt[1]['annotations'][sl], pred[1]['annotations'][sl], gt[0][sl], pred[0][sl])])
+    return boundary.bvpq_compute(clips, cats, out_dir, device=dev, boundary_ratio=ratio)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--videos', type=int, default=2)
     ap.add_argument('--frames', type=int, default=30)
@@ -203,7 +214,14 @@ def main(argv=None):
     ap.add_argument('--flow-max-rad', type=float, default=None, metavar='X', help='one normaliser of the flow colours for all frames (default: each frame its own maximum)')
     ap.add_argument('--stq', action='store_true', help='after the VPQ step, score the same files with tools/eval_stq_device.py: pred/stq.txt and '
                     'pred/stq-tracks.json (off by default)')
-    args = ap.parse_args(argv)
+    ap.add_argument('--boundary', action='store_true', help='after the VPQ step, score the same clips with boundary VPQ (vps_amd.boundary): pred/bvpq-<k>.txt '
+                    'and pred/bvpq-final.txt (off by default)')
+    ap.add_argument('--boundary-ratio', type=float, default=0.02, help='--boundary: width of the band as a fraction of the image diagonal')
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
     dev = torch.device('cuda:0')
     labeled_fid, lambda_ = 20, 5
     overlay = (args.overlay, args.overlay_quality, args.overlay_alpha) if args.overlay else None
@@ -236,6 +254,12 @@ def main(argv=None):
         r = stq(os.path.join(args.out, 'gt' if args.gt_prec else 'pred'), gt[1], os.path.join(args.out, 'pred'), names, args.out, nper, dev)
         report['stq'] = dict(stq=round(100 * r['stq'], 4), aq=round(100 * r['aq'], 4), sq=round(100 * r['sq'], 4), tracks=r['n'])
         print('STQ %.4f  AQ %.4f  SQ %.4f' % (100 * r['stq'], 100 * r['aq'], 100 * r['sq']))
+    if args.boundary:                                   # a key of its own: without the option the report is what it was
+        r = bvpq(gt, pred, args.videos, nper, dev, os.path.join(args.out, 'pred'), args.boundary_ratio)
+        report['bvpq'] = dict(bvpq=round(r['All'], 4), ratio=args.boundary_ratio,
+                              pq_per_window={str(k): round(100 * r['per_window'][k]['All']['pq'], 4) for k in (1, 2, 3, 4)},
+                              biou_per_window={str(k): round(100 * r['per_window'][k]['All']['biou'], 4) for k in (1, 2, 3, 4)})
+        print('boundary VPQ %.4f (VPQ %.4f)' % (r['All'], score['vpq']))
     if overlay_video:                                   # a key of its own: without the option the report is what it was
         report['overlay_video'] = dict(files=overlay_video['files'], sampling=args.overlay_video_sampling)
     with open(os.path.join(args.out, 'report.json'), 'w') as f:

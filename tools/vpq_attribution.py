@@ -67,20 +67,31 @@ def compare(ref, got, args, dev):
     ids = sum(1 for a, b in zip(h0['ids'], h1['ids']) if not (a.shape == b.shape and np.array_equal(a, b)))
     sem = float(np.mean([np.mean(a != b) for a, b in zip(h0['sem'], h1['sem'])]))
     pan = float(np.mean([np.mean(a != b) for a, b in zip(h0['pan'], h1['pan'])]))
-    return dict(vpq=round(score['vpq'], 4), pq_per_window={str(k): round(100 * score[k]['pq'], 4) for k in (1, 2, 3, 4)},
+    extra = {}
+    if args.boundary:               # the boundary VPQ of the same pair beside the mask figure: it sees the contour jitter that mask IoU averages away
+        b = RV.bvpq((ref['pans'], ref['pj']), (got['pans'], got['pj']), args.videos, ref['nper'], dev, None, args.boundary_ratio)
+        extra = dict(boundary_vpq=round(b['All'], 4), boundary_pq_per_window={str(k): round(100 * b['per_window'][k]['All']['pq'], 4) for k in (1, 2, 3, 4)},
+                     mean_boundary_iou_of_matches_per_window={str(k): round(100 * b['per_window'][k]['All']['biou'], 4) for k in (1, 2, 3, 4)})
+    return dict(vpq=round(score['vpq'], 4), pq_per_window={str(k): round(100 * score[k]['pq'], 4) for k in (1, 2, 3, 4)}, **extra,
                 frames=n, frames_with_a_different_instance_list=lists, frames_with_different_ids=ids,
                 semantic_map_pixels_differing=round(sem, 7), panoptic_map_pixels_differing=round(pan, 7), frames_per_s=round(got['fps'], 2))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument('--boundary', action='store_true', help='print the boundary VPQ (vps_amd.boundary) of each mode against exact f32 beside the mask figure')
+    ap.add_argument('--boundary-ratio', type=float, default=0.02)
     ap.add_argument('--videos', type=int, default=2)
     ap.add_argument('--frames', type=int, default=30)
     ap.add_argument('--height', type=int, default=1024)
     ap.add_argument('--width', type=int, default=2048)
     ap.add_argument('--out', default=os.path.join(ROOT, 'gpurun_out', 'vpq_attr'))
     ap.add_argument('--sets', default='near_tied,separated')
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
     dev = torch.device('cuda:0')
     report = dict(size=[args.height, args.width], videos=args.videos, frames_per_video=args.frames, reference='exact fp32 MFMA kernels, default schedule',
                   note='VPQ of each run against the reference run (the reference run is the "ground truth"): 100 = identical panoptic videos')

@@ -15,6 +15,7 @@ from .checkpoint import load_checkpoint  # noqa: F401,E402
 from . import ipq  # noqa: F401,E402  (image-level evaluation: SemanticEvaluator, ImagePanopticUnifier, ImageConverter, pq_compute, evaluate_panoptic)
 from . import flowvis  # noqa: F401,E402  (optical-flow output: flow_colour, FlowWriter, write_flo / read_flo)
 from . import tubes  # noqa: F401,E402  (track tubes: rle_runs, segment_rles, rle_decode, TubeCollector)
+from . import boundary  # noqa: F401,E402  (boundary PQ / boundary VPQ: dilation, boundary_band, pq_compute_single_core, vpq_compute_single_core)
 from .dataloader import DataContainer, LookaheadLoader, MMDataParallel, build_dataloader  # noqa: F401,E402
 
 __version__ = '0.1.0'
