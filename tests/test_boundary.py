@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import boundary_restate as R
+from numpy_seam import numpy_device                            # noqa: F401 (fixture)
 from vps_amd import boundary, hip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -117,38 +118,6 @@ def test_two_frame_tube_one_frame_matches_alone_and_the_summed_bands_do_not():
 
 
 # ---------------------------------------------------------------------------------------------- the host half of vps_amd/boundary.py
-def _numpy_pair_table(g, p, gt_ids, pred_ids, dev):
-    gi, pi = R.ids_of(g.cpu().numpy()), R.ids_of(p.cpu().numpy())
-    r = np.searchsorted(gt_ids, gi); r[(r >= len(gt_ids)) | (gt_ids[np.minimum(r, len(gt_ids) - 1)] != gi)] = len(gt_ids)
-    c = np.searchsorted(pred_ids, pi); c[(c >= len(pred_ids)) | (pred_ids[np.minimum(c, len(pred_ids) - 1)] != pi)] = len(pred_ids)
-    tab = np.zeros((len(gt_ids) + 1, len(pred_ids) + 1), dtype=np.int64)
-    np.add.at(tab, (r, c), 1)
-    return tab
-
-
-def _numpy_count(self, gt_json, pred_json, gt_pan, pred_pan, categories, extra_gt_ids=None):
-    from vps_amd import evaluate as ev
-    gt_ids = np.unique(np.array([0] + [el['id'] for el in gt_json['segments_info']] + list(extra_gt_ids or ()), dtype=np.int64))
-    pred_ids = np.unique(np.array([0] + [el['id'] for el in pred_json['segments_info']], dtype=np.int64))
-    tab = _numpy_pair_table(gt_pan, pred_pan, gt_ids, pred_ids, None)
-    gt_segms, pred_segms = ev._merged(gt_json), ev._merged(pred_json)
-    for j, label in enumerate(pred_ids):
-        if int(label) in pred_segms:
-            pred_segms[int(label)]['area'] = int(tab[:, j].sum())
-    rows, cols = np.nonzero(tab[:-1, :-1])
-    return gt_segms, pred_segms, {(int(gt_ids[r]), int(pred_ids[c])): int(tab[r, c]) for r, c in zip(rows, cols)}
-
-
-@pytest.fixture
-def numpy_device(monkeypatch):
-    """the two device steps (band, pair count) replaced by their NumPy definitions: the host logic around them runs without a GPU"""
-    from vps_amd import evaluate as ev
-    monkeypatch.setattr(boundary, '_pair_table', _numpy_pair_table)
-    monkeypatch.setattr(boundary, 'boundary_band', lambda pan, d=None, ratio=0.02, device='cpu': torch.from_numpy(R.band_map(pan.cpu().numpy(), d)))
-    monkeypatch.setattr(ev.FrameCounts, 'count', _numpy_count)
-    monkeypatch.setattr(ev.FrameCounts, '__init__', lambda self, device='cuda': None)
-
-
 def _same(stat, want, cats):
     for c in cats:
         got = stat[c]

@@ -33,23 +33,8 @@ def parse_args(argv=None):
     return ap.parse_args(argv)
 
 
-def write_table(path, results, metrics):
-    """the layout of vpq-<k>.txt (eval_vpq.py:233-244)"""
-    with open(path, 'w') as f:
-        f.write('=' * 48 + '\n')
-        f.write('{:10s}| {:>5s}  {:>5s}  {:>5s} {:>5s}'.format('', 'PQ', 'SQ', 'RQ', 'N\n'))
-        f.write('-' * (10 + 7 * 4) + '\n')
-        for name, _ in metrics:
-            r = results[name]
-            f.write('{:10s}| {:5.1f}  {:5.1f}  {:5.1f} {:5d}\n'.format(name, 100 * r['pq'], 100 * r['sq'], 100 * r['rq'], r['n']))
-        f.write('{:4s}| {:>5s} {:>5s} {:>5s} {:>6s} {:>7s} {:>7s} {:>7s}\n'.format('IDX', 'PQ', 'SQ', 'RQ', 'IoU', 'TP', 'FP', 'FN'))
-        for idx, r in results['per_class'].items():
-            f.write('{:4d} | {:5.1f} {:5.1f} {:5.1f} {:6.1f} {:7d} {:7d} {:7d}\n'.format(idx, 100 * r['pq'], 100 * r['sq'], 100 * r['rq'], r['iou'],
-                                                                                   r['tp'], r['fp'], r['fn']))
-
-
 def main(argv=None):
-    from vps_amd.evaluate import PQStat, vpq_compute_single_core
+    from vps_amd.evaluate import METRICS, PQStat, pq_results, pq_text, vpq_compute_single_core
     args = parse_args(argv)
     submit_dir, truth_dir, output_dir = args.submit_dir, args.truth_dir, args.submit_dir
     if not os.path.isdir(submit_dir):
@@ -72,7 +57,6 @@ def main(argv=None):
     nvid = len(gt_ann) // nper
     videos = [[(gt_ann[i], pred_ann[i], gt_pans[i], pred_pans[i], images[i]) for i in range(v * len(gt_ann) // nvid, (v + 1) * len(gt_ann) // nvid)]
               for v in range(nvid)]
-    metrics = [('All', None), ('Things', True), ('Stuff', False)]
     caches = [dict() for _ in videos]            # one per video: the frame counts are shared by the four window lengths
     vpq = {'All': [], 'Things': [], 'Stuff': []}
     for nframes in (1, 2, 3, 4):                 # k = 0, 5, 10, 15
@@ -81,13 +65,10 @@ def main(argv=None):
         for v, clip in enumerate(videos):
             stat += vpq_compute_single_core(clip, categories, nframes=nframes, device=args.device, _cache=caches[v])
         k = (nframes - 1) * 5
-        results = {}
-        for name, isthing in metrics:
-            results[name], per_class = stat.pq_average(categories, isthing=isthing)
-            if name == 'All':
-                results['per_class'] = per_class
-        write_table(os.path.join(output_dir, 'vpq-%d.txt' % k), results, metrics)
-        for name, _ in metrics:
+        results = pq_results(stat, categories)
+        with open(os.path.join(output_dir, 'vpq-%d.txt' % k), 'w') as f:       # the layout of eval_vpq.py:233-244
+            f.write(pq_text(results))
+        for name, _ in METRICS:
             vpq[name].append(100 * results[name]['pq'])
         print('==> %d-frame vpq_stat: %.2f sec  %s' % (k, time.time() - t0, [round(vpq[n][-1], 4) for n in ('All', 'Things', 'Stuff')]))
     with open(os.path.join(output_dir, 'vpq-final.txt'), 'w') as f:

@@ -19,10 +19,9 @@ import numpy as np
 import torch
 
 from . import hip
-from .evaluate import PQStat
+from .evaluate import PQStat, count_frame, in_image, match
+from .evaluate import pq_results, pq_text      # noqa: F401  `ipq.pq_results`, `ipq.pq_text`: the shared writers under this module's names
 from .postprocess import DevicePngWriter, PanopticUnifier, _rgb2id
-
-VOID = 0
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -256,130 +255,19 @@ class ImageConverter:
 # ------------------------------------------------------------------------------------------------------------------
 def pq_compute_single_core(gt_jsons, pred_jsons, gt_pans, pred_pans, gt_image_jsons, categories, device='cuda'):
     """`BaseDataset._pq_compute_single_core` (base_dataset.py:338-431) without its `proc_id`: a `PQStat` over the images. The pixel
-    pairs of an image come from `vps_pair_count`; the matching is the reference's, visited in ascending (gt id, pred id) order as
-    `np.unique` gives it, so the IoU sums are the same float64 additions. Like the reference, the predicted segments' `area` is
-    overwritten with the pixel count of the PNG.
+    pairs of an image come from `vps_pair_count` (`evaluate.count_frame`); the matching is the reference's (`evaluate.match`), visited
+    in ascending (gt id, pred id) order as `np.unique` gives it, so the IoU sums are the same float64 additions. Like the reference,
+    the predicted segments' `area` is overwritten with the pixel count of the PNG.
     One deliberate difference: where the reference's PNG / JSON consistency checks (:359, :363, :366) would die with a NameError on
     their undefined `gt_ann`, this raises the KeyError those lines were written to raise (with the image id of `gt_image_jsons`)."""
-    lib = hip.load()
     dev = torch.device(device)
     pq_stat = PQStat()
-
-    def up(a):
-        t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
-        t = t.to(dev).contiguous()
-        assert t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3, 'panoptic PNG as uint8 [H,W,3]'
-        return t
-
     for gt_json, pred_json, gt_pan, pred_pan, gt_image_json in zip(gt_jsons, pred_jsons, gt_pans, pred_pans, gt_image_jsons):
-        g, p = up(gt_pan), up(pred_pan)
-        assert g.shape == p.shape
-        image_id = gt_image_json.get('id') if isinstance(gt_image_json, dict) else None
         gt_segms = {el['id']: el for el in gt_json['segments_info']}
-        pred_segms = {el['id']: el for el in pred_json['segments_info']}
-        gt_ids = np.unique(np.array([VOID] + list(gt_segms), dtype=np.int64))
-        pred_ids = np.unique(np.array([VOID] + list(pred_segms), dtype=np.int64))
-        gi = torch.from_numpy(gt_ids.astype(np.int32)).to(dev); pi = torch.from_numpy(pred_ids.astype(np.int32)).to(dev)   # ids < 2^24
-        counts = torch.empty((len(gt_ids) + 1) * (len(pred_ids) + 1), dtype=torch.int32, device=dev)
-        hip.check(lib.vps_pair_count(hip.ptr(g), hip.ptr(p), g.shape[0] * g.shape[1], hip.ptr(gi), len(gt_ids), hip.ptr(pi), len(pred_ids),
-                                     hip.ptr(counts), hip.stream_ptr()), 'vps_pair_count')
-        tab = counts.view(len(gt_ids) + 1, len(pred_ids) + 1).cpu().numpy().astype(np.int64)
-
-        # predicted segments area calculation + prediction sanity checks (:352-366)
-        if tab[:, -1].sum() > 0:                               # a predicted id that is neither listed nor VOID
-            ids = (lambda q: q[:, :, 0] + q[:, :, 1] * 256 + q[:, :, 2] * 65536)(p.cpu().numpy().astype(np.int64))
-            bad = [int(v) for v in np.unique(ids) if v not in pred_segms and v != VOID]
-            raise KeyError('In the image with ID {} segment with ID {} is presented in PNG and not presented in JSON.'.format(image_id, bad[0]))
-        col = tab.sum(0)
-        pred_labels_set = set(el['id'] for el in pred_json['segments_info'])
-        for j, label in enumerate(pred_ids):
-            label = int(label)
-            if col[j] == 0 or label not in pred_segms:         # not in the PNG / VOID that the JSON does not list
-                continue
-            pred_segms[label]['area'] = int(col[j])
-            pred_labels_set.remove(label)
-            if pred_segms[label]['category_id'] not in categories:
-                raise KeyError('In the image with ID {} segment with ID {} has unknown category_id {}.'.format(
-                    image_id, label, pred_segms[label]['category_id']))
-        if len(pred_labels_set) != 0:
-            raise KeyError('In the image with ID {} the following segment IDs {} are presented in JSON and not presented in PNG.'.format(
-                image_id, list(pred_labels_set)))
-
-        # confusion matrix (:368-375): listed ids only - an unlisted ground-truth id never takes part in the matching
-        gt_pred_map = {}
-        rows, cols = np.nonzero(tab[:-1, :-1])                 # row-major: ascending gt id, then pred id
-        for r, c in zip(rows, cols):
-            gt_pred_map[(int(gt_ids[r]), int(pred_ids[c]))] = int(tab[r, c])
-
-        # count all matched pairs (:377-403)
-        gt_matched, pred_matched = set(), set()
-        for (gt_label, pred_label), intersection in gt_pred_map.items():
-            if gt_label not in gt_segms:
-                continue
-            if pred_label not in pred_segms:
-                continue
-            if gt_segms[gt_label]['iscrowd'] == 1:
-                continue
-            if gt_segms[gt_label]['category_id'] != pred_segms[pred_label]['category_id']:
-                continue
-            union = pred_segms[pred_label]['area'] + gt_segms[gt_label]['area'] - intersection - gt_pred_map.get((VOID, pred_label), 0)
-            iou = intersection / union
-            if iou > 0.5:
-                pq_stat[gt_segms[gt_label]['category_id']].tp += 1
-                pq_stat[gt_segms[gt_label]['category_id']].iou += iou
-                gt_matched.add(gt_label)
-                pred_matched.add(pred_label)
-
-        # count false negatives (:405-415)
-        crowd_labels_dict = {}
-        for gt_label, gt_info in gt_segms.items():
-            if gt_label in gt_matched:
-                continue
-            if gt_info['iscrowd'] == 1:                        # crowd segments are ignored
-                crowd_labels_dict[gt_info['category_id']] = gt_label
-                continue
-            pq_stat[gt_info['category_id']].fn += 1
-
-        # count false positives (:417-430)
-        for pred_label, pred_info in pred_segms.items():
-            if pred_label in pred_matched:
-                continue
-            intersection = gt_pred_map.get((VOID, pred_label), 0)
-            if pred_info['category_id'] in crowd_labels_dict:
-                intersection += gt_pred_map.get((crowd_labels_dict[pred_info['category_id']], pred_label), 0)
-            if intersection / pred_info['area'] > 0.5:         # mostly over VOID and CROWD regions: ignored
-                continue
-            pq_stat[pred_info['category_id']].fp += 1
+        pred_segms = {el['id']: el for el in pred_json['segments_info']}       # the caller's entries: their `area` is overwritten
+        gt_pred_map = count_frame(gt_json, pred_json, gt_pan, pred_pan, pred_segms, categories, dev, where=in_image(gt_image_json))[0]
+        match(pq_stat, gt_segms, pred_segms, gt_pred_map)
     return pq_stat
-
-
-def pq_results(pq_stat, categories):
-    """base_dataset.py:189-194: the averages over all / thing / stuff categories, `per_class` from the first"""
-    metrics = [("All", None), ("Things", True), ("Stuff", False)]
-    results = {}
-    for name, isthing in metrics:
-        results[name], per_class_results = pq_stat.pq_average(categories, isthing=isthing)
-        if name == 'All':
-            results['per_class'] = per_class_results
-    return results
-
-
-def pq_text(results):
-    """the text of pq.txt (base_dataset.py:202-209)"""
-    metrics = [("All", None), ("Things", True), ("Stuff", False)]
-    out = []
-    out.append("================================================\n")
-    out.append("{:10s}| {:>5s}  {:>5s}  {:>5s} {:>5s}".format("", "PQ", "SQ", "RQ", "N\n"))
-    out.append("-" * (10 + 7 * 4) + '\n')
-    for name, _isthing in metrics:
-        out.append("{:10s}| {:5.1f}  {:5.1f}  {:5.1f} {:5d}\n".format(name, 100 * results[name]['pq'], 100 * results[name]['sq'],
-                                                                       100 * results[name]['rq'], results[name]['n']))
-    out.append("{:4s}| {:>5s} {:>5s} {:>5s} {:>6s} {:>7s} {:>7s} {:>7s}\n".format("IDX", "PQ", "SQ", "RQ", "IoU", "TP", "FP", "FN"))
-    for idx, result in results['per_class'].items():
-        out.append("{:4d} | {:5.1f} {:5.1f} {:5.1f} {:6.1f} {:7d} {:7d} {:7d}\n".format(idx, 100 * result['pq'], 100 * result['sq'],
-                                                                                        100 * result['rq'], result['iou'], result['tp'],
-                                                                                        result['fp'], result['fn']))
-    return ''.join(out)
 
 
 def pq_compute(gt_jsons, pred_jsons, gt_pans, pred_pans, categories, output_dir, device='cuda'):
