@@ -659,6 +659,33 @@ int vps_stq_accumulate(const uint8_t* gt_rgb, const uint8_t* pred_rgb, int64_t n
                        int64_t* pred_size, int64_t* inter, void* stream);
 int vps_stq_lds_cells(void);
 
+/* Temporal consistency without ground truth (csrc/tc_ops.hip, vps_amd/tc.py): the counting pass of the flow-warped map
+ * agreement for ONE (prev, cur, flow) pair of a video, in one launch on `stream`; does not synchronise or allocate. The definition the
+ * counts follow is restated in vps_amd/tc.py.
+ *   prev, cur    DEVICE uint8 [H][W][3] unified maps (pan_seg, pan_ins, pan_obj); any byte alignment, nothing outside their 3 H W bytes is
+ *                read
+ *   flow         DEVICE fp32 NHWC map, pixel p at flow[p * flow_ld + flow_coff] (x) and [.. + 1] (y), as vps_flow_colour; it points from cur
+ *                to prev: warped(p) = prev(p + flow(p)), the convention of vps_resample2d. Read as 16-byte loads when it is the dense
+ *                [h,w,2] copy on a 16-byte boundary, as 8-byte loads when flow_ld is even and flow + flow_coff is 8-byte aligned
+ *   id_channel   1 or 2: key = map[.., 0] * 256 + map[.., id_channel] (as vps_segment_stats_ch)
+ *   seg_class    HOST uint8 [256], copied into the launch: class index of every pan_seg value; a value >= num_classes is void (= index C)
+ *   keys         DEVICE sorted unique uint16 [nkeys] keys of the video's tracks (NULL when nkeys == 0)
+ *   conf [C+1][C+1], prev_size [nkeys], cur_size [nkeys], same [nkeys], misc [2] = {in view, outside}: DEVICE int64, 8-byte aligned,
+ *                caller-owned; the call ADDS to them and never zeroes them (as vps_stq_accumulate)
+ *   flicker      NULL, or DEVICE uint8 [H][W], every byte written: 0 agrees, 1 class differs, 2 same class and both keys listed and
+ *                different, 3 not in view
+ * Per pixel p = (x, y) of cur, fp32: sx = float(x) + u, sy = float(y) + v, qx = floorf(sx + 0.5f), qy = floorf(sy + 0.5f); in view iff
+ * 0 <= qx <= W-1 and 0 <= qy <= H-1 as floats (NaN, inf fall out), else misc[1] += 1 and nothing else. In view, a = cur[p], b = prev[q]:
+ * misc[0] += 1, conf[c(b)][c(a)] += 1, cur_size[k] += 1 when a's key is listed, prev_size[k] += 1 when b's is, same[k] += 1 when both are
+ * and equal. Tables of at most vps_stq_lds_cells() cells in all ((C+1)^2 + 3 nkeys + 2) are counted in a workgroup-private LDS image and
+ * added with one 64-bit atomic per non-zero cell and workgroup; larger ones take 64-bit global atomics per run of equal pairs. Both give
+ * the same tables. Errors before any launch: -1001 null pointer, -1002 H or W < 1 or H W >= 2^31, -1003 num_classes outside 1..63,
+ * -1004 nkeys outside 0..65536, -1005 id_channel not 1 or 2, -1006 a table that is not 8-byte aligned, -1007 flow_coff < 0 or
+ * flow_ld < flow_coff + 2. */
+int vps_tc_accumulate(const uint8_t* prev, const uint8_t* cur, int H, int W, const float* flow, int flow_ld, int flow_coff, int id_channel,
+                      const uint8_t* seg_class, int num_classes, const uint16_t* keys, int nkeys, int64_t* conf, int64_t* prev_size,
+                      int64_t* cur_size, int64_t* same, int64_t* misc, uint8_t* flicker, void* stream);
+
 /* Boundary PQ / boundary VPQ (csrc/boundary_ops.hip, vps_amd/boundary.py): the boundary band of EVERY segment of a
  * panoptic map in one call, the device form of Boundary IoU's mask_to_boundary (Cheng et al., CVPR 2021) applied per segment.
  *   pan_rgb   DEVICE uint8 [H][W][3] panoptic map (segment id = R + 256 G + 65536 B, the maps vps_pair_count reads); any byte alignment,

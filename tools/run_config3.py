@@ -74,6 +74,11 @@ def parse_args(argv=None):
     ap.add_argument('--boundary', action='store_true', help='with the VPQ step: also write bvpq-<k>.txt and bvpq-final.txt, boundary VPQ (vps_amd.boundary; needs '
                     'the ground truth; off by default)')
     ap.add_argument('--boundary-ratio', type=float, default=0.02, help='--boundary: width of the band as a fraction of the image diagonal')
+    ap.add_argument('--tc', action='store_true', help='temporal consistency without ground truth (vps_amd.tc): every frame against the previous one of its '
+                    'video warped by the detector\'s own flow; tc.txt and tc-tracks.json beside pred.json, also with --video (keeps the flow of every frame '
+                    'on the device until the maps are unified and its pair is counted, 16.8 MB per frame at 1024x2048; off by default)')
+    ap.add_argument('--tc-map', default=None, metavar='DIR', help='--tc: write DIR/<name>.jpg for every frame but a video\'s first, the inconsistency map '
+                    'blended over the frame (red: class differs, amber: track differs, blue: not in view); keeps the decoded frames like --overlay')
     ap.add_argument('--dry-run', action='store_true')
     ap.add_argument('--dry-size', default='128x256'); ap.add_argument('--dry-videos', type=int, default=1); ap.add_argument('--dry-frames', type=int, default=16)
     ap.add_argument('--check-only', action='store_true')
@@ -206,7 +211,8 @@ def run(args, tmp):
     model.ensure_packed(dev)
     prep = DeviceImagePrep(**cfg.img_norm_cfg, size_divisor=32, img_scale=(2048, 1024), device=dev)
     files = [os.path.join(img_prefix, x['file_name']) for x in info]
-    keep = bool(args.overlay or args.overlay_video)
+    keep = bool(args.overlay or args.overlay_video or args.tc_map)
+    with_tc = bool(args.tc or args.tc_map)
     if reader is not None:
         assert len(reader) > 0, '%s holds no complete frame' % args.video
         feeder = ClipFeeder(reader, prep, workers=args.png_workers, keep_frames=keep, y4m_matrix=args.video_matrix).start()
@@ -218,6 +224,9 @@ def run(args, tmp):
         from vps_amd.flowvis import FlowWriter, flow_name
         model.keep_flow = True
         flow_writer = FlowWriter(dev, fmt=args.flow_format, max_rad=args.flow_max_rad, entropy=args.jpeg_entropy)
+    if with_tc:
+        model.keep_flow = True
+        res['all_flows'] = []
     t0 = time.perf_counter()
     with torch.no_grad():
         for idx, im in enumerate(info):
@@ -238,6 +247,8 @@ def run(args, tmp):
                 res['all_frames'].append(feeder.frame(idx))       # the decoded BGR frame the feeder holds anyway
             if flow_writer is not None:
                 flow_writer.submit(result[2]['flow'], flow_name(args.flow, files[idx], args.flow_format))
+            if with_tc:
+                res['all_flows'].append(result[2]['flow'])
     torch.cuda.synchronize()
     if flow_writer is not None:
         flow_files = flow_writer.close()
@@ -274,7 +285,24 @@ def run(args, tmp):
         tb = kw['tubes'].result()
         report['tubes'] = dict(file=os.path.join(output_dir, 'tubes.json'), videos=len(tb['videos']), tracks=sum(len(v['tracks']) for v in tb['videos']))
         kw['tubes'].close()
-    if keep:
+    if with_tc:                                             # a key of its own: without the options the report is what it was
+        from vps_amd import tc
+        nseg = 19                                           # PanopticUnifier(dev, 19, 9): the 19 classes are their own indices, the rest is void
+        seg_class = np.full(256, 255, dtype=np.uint8)
+        seg_class[:nseg] = np.arange(nseg)
+        ev = tc.TcEvaluator(seg_class, nseg, id_channel=2, device=dev, per_pair=True, id_last_stuff=unifier.id_last_stuff)
+        order = sorted(range(len(res['all_names'])), key=lambda i: res['all_names'][i])                # the order of pred_pans_2ch
+        flows = [res['all_flows'][i] for i in order]
+        res['all_flows'] = None                             # `flows` holds them now and lets each one go once its pair is counted
+        tfiles = tc.score_videos(ev, pred_pans_2ch, flows, [res['all_names'][i] for i in order], span, map_dir=args.tc_map,
+                                 frames=[res['all_frames'][i] for i in order] if args.tc_map else None, alpha=args.overlay_alpha,
+                                 quality=args.overlay_quality, entropy=args.jpeg_entropy)
+        r = ev.result()
+        tc.write_outputs(r, output_dir)
+        report['tc'] = dict(tc=round(100 * r['tc'], 4), tc_sem=round(100 * r['tc_sem'], 4), tc_track=round(100 * r['tc_track'], 4), tracks=r['n_tracks'],
+                            in_view_share=round(r['in_view_share'], 6), pairs=len(r['per_pair']), map_files=len(tfiles), file=os.path.join(output_dir, 'tc.txt'))
+        print('TC %.4f  TC_sem %.4f  TC_track %.4f' % (100 * r['tc'], 100 * r['tc_sem'], 100 * r['tc_track']))
+    if keep and (args.overlay or args.overlay_video):
         from run_vps_synthetic import ColorGenerator
         from vps_amd.postprocess import write_overlays
         order = sorted(range(len(res['all_names'])), key=lambda i: res['all_names'][i])                # the order of pred_pans_2ch

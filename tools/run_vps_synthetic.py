@@ -54,9 +54,10 @@ def uint8_frame(H, W, seed, shift):
     return synth.synth_frame(H, W, seed=seed, shift=shift, noise=2.0 if shift != (0, 0) else 0.0).astype(np.uint8)
 
 
-def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg_entropy='host'):
+def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg_entropy='host', keep_flows=False):
     """test_vpq.py:129-149 + single_gpu_test (:28-69) on `videos` synthetic clips -> pano_results with DEVICE maps.
-    `flow` = (directory, format, max_rad): the FlowNet2 flow of EVERY frame as DIR/<name>.<format> (flowvis.FlowWriter)"""
+    `flow` = (directory, format, max_rad): the FlowNet2 flow of EVERY frame as DIR/<name>.<format> (flowvis.FlowWriter).
+    `keep_flows` (--tc): the device flow of every frame in res['all_flows'], 8 bytes per pixel and frame until `tc` has counted its pair"""
     import vps_amd
     from vps_amd import nhwc, synth
     from vps_amd.pipeline import DeviceImagePrep, PairFeeder
@@ -78,6 +79,9 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg
         from vps_amd.flowvis import FlowWriter, flow_name
         model.keep_flow = True
         flow_writer = FlowWriter(dev, fmt=flow[1], max_rad=flow[2], entropy=jpeg_entropy)
+    if keep_flows:
+        model.keep_flow = True
+        res['all_flows'] = []
     decoded = [[uint8_frame(H, W, seed=v, shift=(2 * f, f)) for f in range(nframes)] for v in range(videos)]   # "cv2.imread" results (BGR uint8)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -98,6 +102,8 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg
             res['all_frames'].append(decoded[v][f])                                # the decoded frame itself: what --overlay draws on
             if flow_writer is not None:
                 flow_writer.submit(result[2]['flow'], flow_name(flow[0], name, flow[1]))
+            if keep_flows:
+                res['all_flows'].append(result[2]['flow'])
     if flow_writer is not None:
         res['flow_files'] = flow_writer.close()
     torch.cuda.synchronize()
@@ -105,19 +111,23 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg
 
 
 def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_png=False, overlay=None, tubes=False, jpeg_entropy='host',
-                overlay_video=None):
+                overlay_video=None, tc=None):
     """test_vpq.py:178-198 with the device-side unifier / converter / asynchronous writer (`device_png`: the PNGs are filtered and
     deflated on the device too, postprocess.DevicePngWriter). `overlay` = (directory, quality, alpha): an overlay JPEG of EVERY frame,
     blended and transformed on the device (postprocess.write_overlays). `tubes`: tubes.json beside pred.json, the COCO run-length
     encoding, box and area of every tracked instance in every labelled frame (vps_amd.tubes). `overlay_video` = (FILE.y4m, sampling):
     the same overlays as one Y4M stream per video (y4m.Y4mWriter), beside the JPEGs or, without `overlay`, instead of them; its
-    'files' entry receives the streams' names"""
+    'files' entry receives the streams' names. `tc` = dict(map_dir, alpha, quality): the temporal consistency of EVERY video's consecutive
+    frames from res['all_flows'] (vps_amd.tc; tc.txt and tc-tracks.json beside pred.json, the inconsistency overlays in map_dir if it
+    is given); its 'result' entry receives the figures"""
     from vps_amd.postprocess import DevicePngWriter, PanopticUnifier, inference_panoptic_video, write_overlays
     unifier = PanopticUnifier(dev, 19, 9)
     two = unifier.get_unified_pan_result(res['all_ssegs'], res['all_panos'], res['all_pano_cls_inds'], obj_ids=res['all_pano_obj_ids'],
                                          stuff_area_limit=2048, names=res['all_names'])
     keys = sorted(two.keys())
     pred_pans_2ch = [two[k] for k in keys]
+    if tc is not None:
+        tc['result'] = tc_score(pred_pans_2ch, res, keys, len(keys) // max(videos, 1), dev, out_dir, unifier.id_last_stuff, tc, jpeg_entropy)
     names = keys[(labeled_fid // lambda_)::lambda_]                               # names of the labelled frames (im_jsons['images'])
     cats = {c['id']: c for c in CATEGORIES}
     writer = DevicePngWriter(dev) if device_png else None
@@ -141,6 +151,28 @@ def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_pn
         write_overlays(pred_pans_2ch, [frames[k] for k in keys], keys, ov[0], ColorGenerator(cats), len(keys) // max(videos, 1), device=dev,
                        quality=ov[1], alpha=ov[2], entropy=jpeg_entropy, **vkw)
     return names, pans, pj
+
+
+def tc_score(maps, res, names, nframes_per_video, dev, out_dir, id_last_stuff, opt, jpeg_entropy='host'):
+    """--tc: the unified maps of every frame (in the order of `names`) against their predecessors warped by the run's own flows. The 19
+    classes of CATEGORIES are the class indices, every other pan_seg value is void; tracks are keyed by pan_obj (channel 2)"""
+    from vps_amd import tc
+    seg_class = np.full(256, 255, dtype=np.uint8)
+    seg_class[:len(CATEGORIES)] = np.arange(len(CATEGORIES))
+    ev = tc.TcEvaluator(seg_class, len(CATEGORIES), id_channel=2, device=dev, per_pair=True, id_last_stuff=id_last_stuff)
+    at = {n: i for i, n in enumerate(res['all_names'])}
+    flows = [res['all_flows'][at[n]] for n in names]
+    res['all_flows'] = None                               # `flows` holds them now and lets each one go once its pair is counted
+    frames = None
+    if opt.get('map_dir'):
+        frames = [np.pad(res['all_frames'][at[n]], ((0, m.shape[0] - res['all_frames'][at[n]].shape[0]), (0, m.shape[1] - res['all_frames'][at[n]].shape[1]),
+                                                     (0, 0)), mode='edge') for n, m in zip(names, maps)]
+    files = tc.score_videos(ev, maps, flows, names, nframes_per_video, map_dir=opt.get('map_dir'), frames=frames, alpha=opt.get('alpha', 128),
+                            quality=opt.get('quality', 90), entropy=jpeg_entropy)
+    result = ev.result()
+    tc.write_outputs(result, out_dir)
+    result['map_files'] = files
+    return result
 
 
 def vpq(gt, pred, videos, nper, dev):
@@ -217,6 +249,11 @@ def parse_args(argv=None):
     ap.add_argument('--boundary', action='store_true', help='after the VPQ step, score the same clips with boundary VPQ (vps_amd.boundary): pred/bvpq-<k>.txt '
                     'and pred/bvpq-final.txt (off by default)')
     ap.add_argument('--boundary-ratio', type=float, default=0.02, help='--boundary: width of the band as a fraction of the image diagonal')
+    ap.add_argument('--tc', action='store_true', help='temporal consistency without ground truth (vps_amd.tc): every frame against the previous one warped by '
+                    'the detector\'s own flow; pred/tc.txt and pred/tc-tracks.json (keeps the flow of every frame on the device until its pair is counted; '
+                    'off by default)')
+    ap.add_argument('--tc-map', default=None, metavar='DIR', help='--tc: write DIR/<name>.jpg for every frame but a video\'s first, the inconsistency map '
+                    'blended over the frame (red: class differs, amber: track differs, blue: not in view)')
     return ap.parse_args(argv)
 
 
@@ -228,10 +265,11 @@ def main(argv=None):
     overlay_video = dict(file=args.overlay_video, sampling=args.overlay_video_sampling, files=[], alpha=args.overlay_alpha) if args.overlay_video else None
     nper = len(range(labeled_fid // lambda_, args.frames, lambda_))
     flow = (args.flow, args.flow_format, args.flow_max_rad) if args.flow else None
-    res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated, flow, args.jpeg_entropy)
+    tc = dict(map_dir=args.tc_map, alpha=args.overlay_alpha, quality=args.overlay_quality) if (args.tc or args.tc_map) else None
+    res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated, flow, args.jpeg_entropy, keep_flows=tc is not None)
     t0 = time.perf_counter()
     names, pans, pj = postprocess(res, os.path.join(args.out, 'pred'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png, overlay, args.tubes,
-                                  args.jpeg_entropy, overlay_video)
+                                  args.jpeg_entropy, overlay_video, tc)
     dpost = time.perf_counter() - t0
     pred = (pans, pj)
     gt = pred
@@ -260,6 +298,11 @@ def main(argv=None):
                               pq_per_window={str(k): round(100 * r['per_window'][k]['All']['pq'], 4) for k in (1, 2, 3, 4)},
                               biou_per_window={str(k): round(100 * r['per_window'][k]['All']['biou'], 4) for k in (1, 2, 3, 4)})
         print('boundary VPQ %.4f (VPQ %.4f)' % (r['All'], score['vpq']))
+    if tc:                                              # a key of its own: without the option the report is what it was
+        r = tc['result']
+        report['tc'] = dict(tc=round(100 * r['tc'], 4), tc_sem=round(100 * r['tc_sem'], 4), tc_track=round(100 * r['tc_track'], 4), tracks=r['n_tracks'],
+                            in_view_share=round(r['in_view_share'], 6), pairs=len(r['per_pair']), map_files=len(r['map_files']))
+        print('TC %.4f  TC_sem %.4f  TC_track %.4f' % (100 * r['tc'], 100 * r['tc_sem'], 100 * r['tc_track']))
     if overlay_video:                                   # a key of its own: without the option the report is what it was
         report['overlay_video'] = dict(files=overlay_video['files'], sampling=args.overlay_video_sampling)
     with open(os.path.join(args.out, 'report.json'), 'w') as f:

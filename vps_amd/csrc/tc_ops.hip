@@ -1,0 +1,248 @@
+// Temporal consistency without ground truth (vps_amd/tc.py): the counting pass of the flow-warped map agreement.
+//   vps_tc_accumulate      one (prev, cur, flow) pair: prev is read at p + flow(p) for every pixel p of cur and the (warped, cur) pixel
+//                          pairs are ADDED to the caller's int64 tables - the class confusion matrix, the sizes of the listed tracks in
+//                          both maps and their agreement, the in-view / outside counts. Optionally one byte per pixel says how the
+//                          pixel disagrees. The tables stay on the device; nothing is zeroed, downloaded or synchronised here.
+// Integer adds only: the result does not depend on their order, so two runs (and the two table paths) give identical tables.
+#include "common.h"
+#include <string.h>
+
+namespace {
+
+constexpr int TC_THREADS = 256;
+constexpr int TC_PIX = 4;                             // pixels of cur per lane and step: 12 bytes = 3 dwords of the map, 4 bytes of the output
+
+struct TcClasses { uint32_t w[64]; };                 // seg_class[256], handed over in the kernel arguments
+struct TcTables { unsigned long long *conf, *prev_size, *cur_size, *same, *misc; };
+
+__device__ __forceinline__ int tc_key_index(const uint16_t* __restrict__ keys, int n, uint32_t v) {
+    int lo = 0, hi = n - 1;
+    while (lo <= hi) {                                // sorted, unique
+        const int mid = (lo + hi) >> 1;
+        const uint32_t m = keys[mid];
+        if (m == v) return mid;
+        if (m < v) lo = mid + 1; else hi = mid - 1;
+    }
+    return n;                                         // not listed
+}
+
+// The three bytes (as one 24-bit value, channel 0 lowest) of pixels 4 * ch .. 4 * ch + n - 1 of a [npix][3] byte map whose base need not
+// be dword-aligned: the 12 bytes sit in 3 aligned dwords (4 when the base is off a dword boundary), loaded as dwords and shifted into
+// place. A chunk whose dwords would reach in front of the base or past byte 3 * npix is read byte by byte (stq_ops.hip has the same).
+__device__ __forceinline__ void tc_load_px(const uint8_t* __restrict__ p, long nbytes, long ch, int n, uint32_t (&px)[TC_PIX]) {
+    const unsigned o = (unsigned)((uintptr_t)p & 3);
+    const long b0 = 12 * ch;                          // first byte of the chunk's dwords, counted from the aligned address p - o
+    if (b0 >= (long)o && b0 + (o ? 16 : 12) <= (long)o + nbytes) {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(p - o) + 3 * ch;
+        const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = o ? w[3] : 0u;
+        const uint32_t d0 = __builtin_amdgcn_alignbyte(w1, w0, o), d1 = __builtin_amdgcn_alignbyte(w2, w1, o),
+                       d2 = __builtin_amdgcn_alignbyte(w3, w2, o);
+        px[0] = d0 & 0xffffffu;
+        px[1] = (d0 >> 24) | ((d1 & 0xffffu) << 8);
+        px[2] = (d1 >> 16) | ((d2 & 0xffu) << 16);
+        px[3] = d2 >> 8;
+    } else {
+#pragma unroll
+        for (int i = 0; i < TC_PIX; ++i) {
+            px[i] = 0;
+            if (i < n) {
+                const uint8_t* a = p + b0 + 3 * i;
+                px[i] = a[0] | (a[1] << 8) | (a[2] << 16);
+            }
+        }
+    }
+}
+
+// the cells one run of in-view (warped, cur) pairs adds to; -1 = none
+struct TcCells { int conf, prev, cur, same; };
+
+template <bool LDS>
+__device__ __forceinline__ void tc_add(const TcCells& c, uint32_t n, uint32_t* tab, int o_prev, int o_cur, int o_same, const TcTables& t) {
+    if (LDS) {
+        atomicAdd(&tab[c.conf], n);
+        if (c.prev >= 0) atomicAdd(&tab[o_prev + c.prev], n);
+        if (c.cur >= 0) atomicAdd(&tab[o_cur + c.cur], n);
+        if (c.same >= 0) atomicAdd(&tab[o_same + c.same], n);
+    } else {
+        atomicAdd(&t.conf[c.conf], (unsigned long long)n);
+        if (c.prev >= 0) atomicAdd(&t.prev_size[c.prev], (unsigned long long)n);
+        if (c.cur >= 0) atomicAdd(&t.cur_size[c.cur], (unsigned long long)n);
+        if (c.same >= 0) atomicAdd(&t.same[c.same], (unsigned long long)n);
+    }
+}
+
+// A lane owns 4 consecutive pixels of cur (linear index, a chunk may run over the end of a row): cur as aligned dwords, the flow as two
+// 16-byte loads (fmode 2: dense [h,w,2], 16-byte aligned), one 8-byte load per pixel (fmode 1) or two 4-byte ones (fmode 0), the two
+// bytes of prev that the pair needs from wherever the flow points. Equal neighbouring (warped, cur, in view) states are folded in
+// registers and resolved to their cells once per run (two table lookups, up to two binary searches); the run a lane ends with is
+// compared across the wavefront and, where every lane holds the same one, summed by shuffles and added by one lane. The in-view /
+// outside counts stay in registers until the end. LDS = true: the adds go to the workgroup's own uint32 image (conf | prev_size |
+// cur_size | same | misc) and leave as one 64-bit atomic per non-zero cell; LDS = false: 64-bit global atomics per run. No workgroup
+// reads what another one writes.
+template <bool LDS>
+__global__ __launch_bounds__(TC_THREADS)
+void tc_accumulate_kernel(const uint8_t* __restrict__ prev, const uint8_t* __restrict__ cur, int H, int W, const float* __restrict__ flow, int ld,
+                          int coff, int fmode, int idch, TcClasses sc, int C, const uint16_t* __restrict__ keys, int nkeys, TcTables t,
+                          uint8_t* __restrict__ flick) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t tc_lds[];
+    const uint8_t* cls = reinterpret_cast<const uint8_t*>(tc_lds);             // 256 bytes in front of the tables
+    uint32_t* tab = tc_lds + 64;
+    const int C1 = C + 1, o_prev = C1 * C1, o_cur = o_prev + nkeys, o_same = o_cur + nkeys, o_misc = o_same + nkeys, cells = o_misc + 2;
+    if (threadIdx.x < 64) tc_lds[threadIdx.x] = sc.w[threadIdx.x];
+    if (LDS)
+        for (int i = threadIdx.x; i < cells; i += TC_THREADS) tab[i] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const long npix = (long)H * W, nbytes = 3 * npix, nchunk = (npix + TC_PIX - 1) / TC_PIX;
+    const float xmax = (float)(W - 1), ymax = (float)(H - 1);
+    const int sh = 8 * idch;
+    const bool flick4 = flick && ((uintptr_t)flick & 3) == 0;
+    uint32_t n_in = 0, n_out = 0;
+    for (long ch0 = (long)blockIdx.x * TC_THREADS; ch0 < nchunk; ch0 += (long)gridDim.x * TC_THREADS) {       // uniform per workgroup
+        const long ch = ch0 + threadIdx.x;
+        uint32_t run_st = 0, run_len = 0, code = 0;
+        bool run_in = false;
+        TcCells cell = {-1, -1, -1, -1};
+        if (ch < nchunk) {
+            const long p0 = TC_PIX * ch;
+            const int n = (int)min((long)TC_PIX, npix - p0);
+            uint32_t A[TC_PIX];
+            tc_load_px(cur, nbytes, ch, n, A);
+            float u[TC_PIX], v[TC_PIX];
+            if (fmode == 2 && n == TC_PIX) {
+                const float4 f0 = *reinterpret_cast<const float4*>(flow + 2 * p0), f1 = *reinterpret_cast<const float4*>(flow + 2 * p0 + 4);
+                u[0] = f0.x; v[0] = f0.y; u[1] = f0.z; v[1] = f0.w; u[2] = f1.x; v[2] = f1.y; u[3] = f1.z; v[3] = f1.w;
+            } else {
+#pragma unroll
+                for (int i = 0; i < TC_PIX; ++i) {
+                    u[i] = v[i] = 0.f;
+                    if (i < n) {
+                        const float* f = flow + (p0 + i) * ld + coff;
+                        if (fmode >= 1) { const float2 g = *reinterpret_cast<const float2*>(f); u[i] = g.x; v[i] = g.y; }
+                        else { u[i] = f[0]; v[i] = f[1]; }
+                    }
+                }
+            }
+            int y = (int)(p0 / W), x = (int)(p0 - (long)y * W);
+            uint32_t codes = 0;
+#pragma unroll
+            for (int i = 0; i < TC_PIX; ++i) {
+                if (i >= n) break;
+                // ---- the definition's warp: fp32, one add each, compared as floats before any conversion
+                const float sx = (float)x + u[i], sy = (float)y + v[i];
+                const float qx = floorf(sx + 0.5f), qy = floorf(sy + 0.5f);
+                bool in = qx >= 0.f && qx <= xmax && qy >= 0.f && qy <= ymax;
+                int ix = 0, iy = 0;
+                if (in) {
+                    ix = (int)qx; iy = (int)qy;
+                    in = ix < W && iy < H;            // (float)(W - 1) is W itself for some W above 2^24: never read past the map
+                }
+                uint32_t st = 0;
+                if (in) {
+                    const uint8_t* b = prev + 3 * ((long)iy * W + ix);
+                    st = (((A[i] & 0xffu) << 8) | ((A[i] >> sh) & 0xffu)) | ((uint32_t)b[0] << 24) | ((uint32_t)b[idch] << 16);
+                    ++n_in;
+                } else {
+                    ++n_out;
+                }
+                if (!run_len || in != run_in || st != run_st) {
+                    if (run_len && run_in) tc_add<LDS>(cell, run_len, tab, o_prev, o_cur, o_same, t);
+                    run_in = in; run_st = st; run_len = 0;
+                    code = 3;
+                    if (in) {                         // ---- the definition's per-pixel rules, once per run
+                        const uint32_t ak = st & 0xffffu, bk = st >> 16;
+                        int ca = cls[ak >> 8], cb = cls[bk >> 8];
+                        if (ca > C) ca = C;
+                        if (cb > C) cb = C;
+                        const int ka = tc_key_index(keys, nkeys, ak), kb = ak == bk ? ka : tc_key_index(keys, nkeys, bk);
+                        cell.conf = cb * C1 + ca;
+                        cell.cur = ka < nkeys ? ka : -1;
+                        cell.prev = kb < nkeys ? kb : -1;
+                        cell.same = ka < nkeys && ka == kb ? ka : -1;
+                        code = ca != cb ? 1 : (ka < nkeys && kb < nkeys && ka != kb ? 2 : 0);
+                    }
+                }
+                ++run_len;
+                codes |= code << (8 * i);
+                if (++x == W) { x = 0; ++y; }
+            }
+            if (flick) {
+                if (flick4 && n == TC_PIX) {
+                    *reinterpret_cast<uint32_t*>(flick + p0) = codes;
+                } else {
+                    for (int i = 0; i < n; ++i) flick[p0 + i] = (uint8_t)(codes >> (8 * i));
+                }
+            }
+        }
+        // the in-view run each lane is left with: one add per wavefront where all of them are the same
+        const bool has = run_len > 0;
+        const unsigned long long act = __ballot(has);
+        if (act) {
+            const int src = __ffsll((long long)act) - 1;
+            const uint32_t fs = __shfl(run_st, src, 64);
+            if (__ballot(has && (!run_in || run_st != fs)) == 0) {
+                uint32_t sum = has ? run_len : 0;
+                for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
+                if (lane == src) tc_add<LDS>(cell, sum, tab, o_prev, o_cur, o_same, t);
+            } else if (has && run_in) {
+                tc_add<LDS>(cell, run_len, tab, o_prev, o_cur, o_same, t);
+            }
+        }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        n_in += __shfl_xor(n_in, off, 64);
+        n_out += __shfl_xor(n_out, off, 64);
+    }
+    if (lane == 0) {
+        if (LDS) {
+            if (n_in) atomicAdd(&tab[o_misc], n_in);
+            if (n_out) atomicAdd(&tab[o_misc + 1], n_out);
+        } else {
+            if (n_in) atomicAdd(&t.misc[0], (unsigned long long)n_in);
+            if (n_out) atomicAdd(&t.misc[1], (unsigned long long)n_out);
+        }
+    }
+    if (LDS) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < cells; i += TC_THREADS) {
+            const uint32_t val = tab[i];
+            if (!val) continue;
+            unsigned long long* dst = i < o_prev ? t.conf + i : i < o_cur ? t.prev_size + (i - o_prev) : i < o_same ? t.cur_size + (i - o_cur)
+                                    : i < o_misc ? t.same + (i - o_same) : t.misc + (i - o_misc);
+            atomicAdd(dst, (unsigned long long)val);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int vps_tc_accumulate(const uint8_t* prev, const uint8_t* cur, int H, int W, const float* flow, int flow_ld, int flow_coff, int id_channel,
+                                 const uint8_t* seg_class, int num_classes, const uint16_t* keys, int nkeys, int64_t* conf, int64_t* prev_size,
+                                 int64_t* cur_size, int64_t* same, int64_t* misc, uint8_t* flicker, void* stream) {
+    if (!prev || !cur || !flow || !seg_class || !conf || !misc) return VPS_EARG(1);
+    if (H < 1 || W < 1 || (long)H * W >= (1L << 31)) return VPS_EARG(2);       // a workgroup's uint32 cells cannot wrap
+    if (num_classes < 1 || num_classes > 63) return VPS_EARG(3);
+    if (nkeys < 0 || nkeys > 65536) return VPS_EARG(4);
+    if (id_channel != 1 && id_channel != 2) return VPS_EARG(5);
+    if (nkeys > 0 && (!keys || !prev_size || !cur_size || !same)) return VPS_EARG(1);
+    if (((uintptr_t)conf | (uintptr_t)prev_size | (uintptr_t)cur_size | (uintptr_t)same | (uintptr_t)misc) & 7) return VPS_EARG(6);
+    if (flow_coff < 0 || flow_ld < flow_coff + 2) return VPS_EARG(7);
+    TcTables t = {reinterpret_cast<unsigned long long*>(conf), reinterpret_cast<unsigned long long*>(prev_size),
+                  reinterpret_cast<unsigned long long*>(cur_size), reinterpret_cast<unsigned long long*>(same),
+                  reinterpret_cast<unsigned long long*>(misc)};
+    TcClasses sc;
+    memcpy(sc.w, seg_class, 256);                                                // the caller's table may go once the call returns
+    const int fmode = (flow_ld == 2 && flow_coff == 0 && ((uintptr_t)flow & 15) == 0) ? 2
+                    : ((flow_ld & 1) == 0 && ((uintptr_t)(flow + flow_coff) & 7) == 0) ? 1 : 0;
+    const long cells = (long)(num_classes + 1) * (num_classes + 1) + 3L * nkeys + 2;
+    const long nchunk = ((long)H * W + TC_PIX - 1) / TC_PIX;
+    long g = nchunk / (TC_THREADS * 4); if (g > 512) g = 512; if (g < 1) g = 1;            // >= 4 chunks per lane, <= 2 workgroups per CU
+    hipStream_t s = (hipStream_t)stream;
+    if (cells <= vps_stq_lds_cells())                                                       // the path depends on the table sizes alone
+        hipLaunchKernelGGL(tc_accumulate_kernel<true>, dim3((unsigned)g), dim3(TC_THREADS), 256 + sizeof(uint32_t) * cells, s, prev, cur, H, W, flow,
+                           flow_ld, flow_coff, fmode, id_channel, sc, num_classes, keys, nkeys, t, flicker);
+    else
+        hipLaunchKernelGGL(tc_accumulate_kernel<false>, dim3((unsigned)g), dim3(TC_THREADS), 256, s, prev, cur, H, W, flow, flow_ld, flow_coff, fmode,
+                           id_channel, sc, num_classes, keys, nkeys, t, flicker);
+    return vps_launch_status();
+}

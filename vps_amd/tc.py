@@ -1,0 +1,353 @@
+"""Temporal consistency (TC) without ground truth: the agreement of a frame's unified map with the previous frame's map warped to it by
+the detector's own FlowNet2 flow, with the per-pixel counting on the device.
+
+The video-segmentation literature reports such a figure beside accuracy (Liu et al., "Efficient semantic video segmentation with
+per-frame inference", ECCV 2020, warp with FlowNet2 and score the mIoU of the warped and the current prediction). The reference has no
+TC. The definition below is RESTATED FROM MEMORY of that publication and EXTENDED to track ids; no implementation of it is available
+where this was written. It is pinned only by hand-derived answers (tests/test_tc.py) and by an independent per-pixel restatement
+(tests/tc_restate.py), not by a run of an original.
+
+One pair: frame t is "cur", its reference frame (frame t-1 of the same video in these tools) is "prev"; a video's first frame has no
+pair. cur, prev: unified maps uint8 [H][W][3] = (pan_seg, pan_ins, pan_obj). flow: fp32 [H][W][2], channel 0 = x, 1 = y, in the
+direction the detector computes it: FlowNet2 gets (img, ref) and its stages sample the SECOND image at p + flow(p) (flownet2.py
+`run`: x6 = img | ref, every `vps_flow_stage_full` warps ref; `vps_resample2d`: out(p) = in(p + flow(p))), so
+    warped(p) = prev(p + flow(p))
+and `pano_results['flow']` of frame t (`keep_flow`) is the flow of this pair as it stands.
+
+Warp, per pixel p = (x, y) of cur, all in fp32:
+    sx = float(x) + u, sy = float(y) + v (one add each);  qx = floorf(sx + 0.5f), qy = floorf(sy + 0.5f)
+    in view iff 0 <= qx <= W-1 and 0 <= qy <= H-1, compared as floats before any conversion to int: NaN, +-inf, 1e30 fall out
+    not in view: outside += 1 and nothing else
+Semantic table: class index c(.) = seg_class[pan_seg] (uint8 [256] from the host), a value >= C is void = index C. In view, a = cur[p],
+b = prev[q]: conf[c(b)][c(a)] += 1, conf is [C+1][C+1].
+    IoU_c = conf[c][c] / (row_c + col_c - conf[c][c]) over the full table (a pixel that was road and became void costs road)
+    TC_sem = mean of IoU_c over the classes c < C whose union is non-zero (0 when there is none)
+Track tables: key = pan_seg * 256 + map[.., id_channel] (the key of `vps_segment_stats_ch`; id_channel 2 = pan_obj for video maps). The
+host lists the sorted unique uint16 keys of the video's thing segments. In view: cur_size[k] += 1 when cur's key is listed,
+prev_size[k] += 1 when the warped key is listed, same[k] += 1 when both are listed and equal.
+    IoU_k = sum same / sum (prev_size + cur_size - same), summed over the video's pairs (a tube-style sum, like VPQ)
+    TC_track = mean over the keys whose union is non-zero (0 when there is none: a video without tracks has TC 0, read TC_sem then)
+    TC = sqrt(TC_sem * TC_track)
+Over several videos: conf is summed, the tracks of all videos are averaged together.
+
+Known limits: occluded pixels are NOT excluded, so a perfect prediction scores below 1 wherever the flow is wrong; a track that enters
+or leaves the view is charged for it; the figure rates the flow as much as the maps.
+
+`tc_from_tables`, `TcStats` and `tc_text` are NumPy / Python only. The counting (`TcEvaluator`) is `vps_tc_accumulate`
+(csrc/tc_ops.hip): no CPU path, the HIP library must load and a device must be present; host arrays are uploaded, device tensors are
+used as they are. Memory: the evaluator keeps nothing but its tables; a caller that collects the flows of a clip before its maps are
+unified (the tools do) holds 8 bytes per pixel and frame, 16.8 MB per frame at 1024x2048, each until its pair has been counted."""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import hip
+
+MAX_CLASSES = 63
+MAX_KEYS = 65536
+FLICKER_PALETTE = ((0, 0, 0), (255, 0, 0), (255, 200, 0), (0, 90, 255))       # RGB of codes 0..3; 0,0,0 = the overlay keeps the frame
+
+
+def table_sizes(num_classes, nkeys):
+    """cells of (conf, prev_size, cur_size, same, misc) as they lie in one int64 block"""
+    return [(num_classes + 1) ** 2, nkeys, nkeys, nkeys, 2]
+
+
+def _iou_mean(inter, union):
+    iou = np.zeros(len(union), dtype=np.float64)
+    nz = union > 0
+    iou[nz] = inter[nz].astype(np.float64) / union[nz].astype(np.float64)
+    n = int(nz.sum())
+    return (float(iou[nz].sum() / n) if n else 0.0), iou, n
+
+
+def tc_from_tables(conf, prev_size, cur_size, same, misc):
+    """One pair's, one video's or one set's tables -> {'tc', 'tc_sem', 'tc_track', 'n_classes', 'n_tracks', 'class_iou', 'class_inter',
+    'class_union' [C], 'track_iou', 'track_union' [n], 'in_view', 'outside'}. conf [C+1][C+1], the others [n], misc [2], integers."""
+    conf = np.asarray(conf, dtype=np.int64)
+    if conf.ndim == 1:                                   # as it lies in a block of tables
+        conf = conf.reshape(math.isqrt(len(conf)), -1)
+    C = conf.shape[0] - 1
+    assert conf.shape == (C + 1, C + 1) and C >= 1
+    prev_size, cur_size, same = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (prev_size, cur_size, same))
+    assert len(prev_size) == len(cur_size) == len(same)
+    misc = np.asarray(misc, dtype=np.int64).reshape(2)
+    inter = np.diag(conf)[:C].copy()
+    union = (conf.sum(1) + conf.sum(0))[:C] - inter
+    tc_sem, class_iou, n_classes = _iou_mean(inter, union)
+    t_union = prev_size + cur_size - same
+    tc_track, track_iou, n_tracks = _iou_mean(same, t_union)
+    return {'tc': math.sqrt(tc_sem * tc_track), 'tc_sem': tc_sem, 'tc_track': tc_track, 'n_classes': n_classes, 'n_tracks': n_tracks,
+            'class_iou': class_iou, 'class_inter': inter, 'class_union': union, 'track_iou': track_iou, 'track_union': t_union,
+            'in_view': int(misc[0]), 'outside': int(misc[1])}
+
+
+def _share(in_view, outside):
+    return in_view / (in_view + outside) if in_view + outside else 0.0
+
+
+class TcStats:
+    """Host side of the evaluation: collects the downloaded tables of every video and turns them into the result. No device."""
+
+    def __init__(self, seg_class, num_classes):
+        self.seg_class = np.ascontiguousarray(np.asarray(seg_class, dtype=np.uint8).reshape(-1))
+        if len(self.seg_class) != 256:
+            raise ValueError('seg_class is uint8 [256], one class index per pan_seg value; got %d entries' % len(self.seg_class))
+        if not 1 <= int(num_classes) <= MAX_CLASSES:
+            raise ValueError('TC takes 1..%d classes, got %r' % (MAX_CLASSES, num_classes))
+        self.num_classes = int(num_classes)
+        self.videos = []
+
+    def add_tables(self, video_id, keys, conf, prev_size, cur_size, same, misc, pairs=None):
+        """one video's tables; `pairs`: None or the video's per-pair tables, int64 [npairs][cells] in the order of `table_sizes`"""
+        C, keys = self.num_classes, np.asarray(keys, dtype=np.uint16).reshape(-1)
+        conf = np.asarray(conf, dtype=np.int64).reshape(C + 1, C + 1)
+        st = tc_from_tables(conf, prev_size, cur_size, same, misc)
+        st.update(video=len(self.videos) if video_id is None else video_id, keys=keys, conf=conf, prev_size=np.asarray(prev_size, dtype=np.int64),
+                  cur_size=np.asarray(cur_size, dtype=np.int64), same=np.asarray(same, dtype=np.int64), pairs=None)
+        if pairs is not None:
+            pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, sum(table_sizes(C, len(keys))))
+            st['pairs'] = [tc_from_tables(*np.split(row, np.cumsum(table_sizes(C, len(keys)))[:-1])) for row in pairs]
+        self.videos.append(st)
+        return st
+
+    def result(self):
+        """{'tc', 'tc_sem', 'tc_track', 'n_classes', 'n_tracks', 'in_view', 'outside', 'in_view_share', 'conf' (the summed matrix), 'per_class':
+        [{'class', 'iou', 'inter', 'union'}], 'per_video': [{'video', 'tc', 'tc_sem', 'tc_track', 'n_tracks', 'in_view_share'}], 'tracks': [{'video',
+        'key', 'pan_seg', 'id', 'iou', 'same', 'prev_size', 'cur_size'}] (every listed key with pixels, per video in ascending key),
+        'per_pair': [{'video', 'pair', 'tc', 'tc_sem', 'tc_track', 'in_view_share'}] (videos counted with per-pair tables)}:
+        plain Python numbers, lists and strings, so that it survives JSON unchanged"""
+        C = self.num_classes
+        conf = np.zeros((C + 1, C + 1), dtype=np.int64)
+        same, union, in_view, outside = [], [], 0, 0
+        per_video, tracks, per_pair = [], [], []
+        for st in self.videos:
+            conf += st['conf']; in_view += st['in_view']; outside += st['outside']
+            same.append(st['same']); union.append(st['track_union'])
+            per_video.append({'video': st['video'], 'tc': st['tc'], 'tc_sem': st['tc_sem'], 'tc_track': st['tc_track'], 'n_tracks': st['n_tracks'],
+                              'in_view_share': _share(st['in_view'], st['outside'])})
+            for k in np.nonzero(st['track_union'] > 0)[0]:
+                key = int(st['keys'][k])
+                tracks.append({'video': st['video'], 'key': key, 'pan_seg': key >> 8, 'id': key & 255, 'iou': float(st['track_iou'][k]),
+                               'same': int(st['same'][k]), 'prev_size': int(st['prev_size'][k]), 'cur_size': int(st['cur_size'][k])})
+            for i, p in enumerate(st['pairs'] or []):
+                per_pair.append({'video': st['video'], 'pair': i + 1, 'tc': p['tc'], 'tc_sem': p['tc_sem'], 'tc_track': p['tc_track'],
+                                 'in_view_share': _share(p['in_view'], p['outside'])})
+        cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
+        tot = tc_from_tables(conf, [], [], [], [in_view, outside])                              # the classes of the summed matrix
+        tc_track, _, n_tracks = _iou_mean(cat(same), cat(union))                                # the tracks of all videos together
+        return {'tc': math.sqrt(tot['tc_sem'] * tc_track), 'tc_sem': tot['tc_sem'], 'tc_track': tc_track, 'n_classes': tot['n_classes'],
+                'n_tracks': n_tracks, 'in_view': in_view, 'outside': outside, 'in_view_share': _share(in_view, outside), 'conf': conf.tolist(),
+                'per_class': [{'class': c, 'iou': float(tot['class_iou'][c]), 'inter': int(tot['class_inter'][c]), 'union': int(tot['class_union'][c])}
+                              for c in range(C)],
+                'per_video': per_video, 'tracks': tracks, 'per_pair': per_pair}
+
+
+def tc_text(result):
+    """the text of tc.txt: the set's TC / TC_sem / TC_track x100 with the number of tracks and the in-view share, the per-class IoU
+    rows, the per-video rows"""
+    out = []
+    out.append('=' * 56 + '\n')
+    out.append('{:10s}| {:>5s}  {:>6s}  {:>8s} {:>5s} {:>7s}\n'.format('', 'TC', 'TC_sem', 'TC_track', 'N', 'INVIEW'))
+    out.append('-' * 56 + '\n')
+    row = '{:10s}| {:5.1f}  {:6.1f}  {:8.1f} {:5d} {:7.2f}\n'
+    out.append(row.format('All', 100 * result['tc'], 100 * result['tc_sem'], 100 * result['tc_track'], result['n_tracks'], 100 * result['in_view_share']))
+    out.append('{:4s}| {:>5s} {:>11s} {:>11s}\n'.format('IDX', 'IoU', 'INTER', 'UNION'))
+    for r in result['per_class']:
+        out.append('{:4d}| {:5.1f} {:11d} {:11d}\n'.format(r['class'], 100 * r['iou'], r['inter'], r['union']))
+    out.append('{:10s}| {:>5s}  {:>6s}  {:>8s} {:>5s} {:>7s}\n'.format('VIDEO', 'TC', 'TC_sem', 'TC_track', 'N', 'INVIEW'))
+    for r in result['per_video']:
+        out.append(row.format(str(r['video']), 100 * r['tc'], 100 * r['tc_sem'], 100 * r['tc_track'], r['n_tracks'], 100 * r['in_view_share']))
+    return ''.join(out)
+
+
+def tc_tracks_json(result):
+    """the content of tc-tracks.json: every track with its IoU and sizes, the per-pair series, the summed class matrix and the counts"""
+    return {'tc': result['tc'], 'tc_sem': result['tc_sem'], 'tc_track': result['tc_track'], 'in_view': result['in_view'], 'outside': result['outside'],
+            'in_view_share': result['in_view_share'], 'conf': result['conf'], 'tracks': result['tracks'], 'per_pair': result['per_pair']}
+
+
+def flicker_colour(flicker):
+    """the inconsistency map uint8 [H,W] (device) painted with `FLICKER_PALETTE`: RGB uint8 [H,W,3] for `render_overlay`, where 0,0,0
+    (agreement) keeps the frame"""
+    lut = torch.tensor(FLICKER_PALETTE, dtype=torch.uint8, device=flicker.device)
+    return lut[flicker.to(torch.int64)]
+
+
+class TcEvaluator(TcStats):
+    """The device side. `add_video(maps, flows)` counts one video into tables that stay on the device until its last pair is enqueued
+    (`vps_tc_accumulate` per pair, no synchronisation between pairs, ONE download per video). per_pair=True: the video gets
+    [npairs][cells] tables and every pair its own slice (still one download); the video's tables are their sum and `result()['per_pair']`
+    is the series that shows where a clip flickers. `add_pair` / `end_video` are the same in steps, for a caller that releases each flow
+    once its pair is counted. id_channel 2 = pan_obj (video maps), 1 = pan_ins. The keys default to the thing keys that
+    `vps_segment_stats_ch` finds in the video's maps (`video_keys`): class not 255 and, with id_last_stuff (PanopticUnifier's), a
+    class above it, else an id > 0."""
+
+    def __init__(self, seg_class, num_classes, id_channel=2, device='cuda', per_pair=False, id_last_stuff=None):
+        super().__init__(seg_class, num_classes)
+        if id_channel not in (1, 2):
+            raise ValueError('id_channel is 1 or 2, got %r' % (id_channel,))
+        self.id_channel, self.per_pair, self.id_last_stuff = int(id_channel), bool(per_pair), id_last_stuff
+        self.device = torch.device(device)
+        if self.device.type != 'cuda' or not torch.cuda.is_available():
+            raise hip.VpsHipError('TcEvaluator counts on the device (vps_tc_accumulate); there is no CPU path and no device is present')
+        self.lib = hip.load()
+        self._stats = None
+        self._open = None
+
+    def _map(self, m):
+        t = torch.from_numpy(np.ascontiguousarray(m)) if isinstance(m, np.ndarray) else m
+        if not (t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3):
+            raise ValueError('unified map as uint8 [H,W,3], got %s %s' % (t.dtype, tuple(t.shape)))
+        return t.to(self.device).contiguous()
+
+    def _flow(self, f):
+        """(tensor kept alive, flow_ld): a dense NHWC view [H,W,2] of a wider map (stride W*ld, ld, 1) is used where it lies"""
+        t = torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f
+        if not (t.dtype == torch.float32 and t.dim() == 3 and t.shape[2] == 2):
+            raise ValueError('flow as fp32 [H,W,2], got %s %s' % (t.dtype, tuple(t.shape)))
+        t = t.to(self.device)
+        sh, sw, sc = t.stride()
+        if not (sc == 1 and sw >= 2 and sh == sw * t.shape[1]):
+            t = t.contiguous()
+        return t, int(t.stride(1))
+
+    def video_keys(self, maps):
+        """sorted unique uint16 keys of the thing segments of `maps` (one `vps_segment_stats_ch` per map, one download)"""
+        present = torch.zeros(65536, dtype=torch.bool, device=self.device)
+        if self._stats is None:
+            self._stats = torch.empty(65536 * 5, dtype=torch.int32, device=self.device)
+        for m in maps:
+            t = self._map(m)
+            hip.check(self.lib.vps_segment_stats_ch(hip.ptr(t), int(t.shape[0]), int(t.shape[1]), self.id_channel, hip.ptr(self._stats),
+                                                    hip.stream_ptr()), 'vps_segment_stats_ch')
+            present |= self._stats.view(65536, 5)[:, 0] > 0
+        keys = torch.nonzero(present).flatten().cpu().numpy()
+        sel = (keys >> 8) != 255
+        sel &= ((keys & 255) > 0) if self.id_last_stuff is None else ((keys >> 8) > self.id_last_stuff)
+        return keys[sel].astype(np.uint16)
+
+    def _begin(self, keys, npairs):
+        keys = np.unique(np.asarray(keys, dtype=np.int64).reshape(-1))
+        if len(keys) and not (0 <= keys[0] and keys[-1] < MAX_KEYS):
+            raise ValueError('keys are pan_seg * 256 + id, 0 .. 65535')
+        keys = keys.astype(np.uint16)
+        cells = sum(table_sizes(self.num_classes, len(keys)))
+        self._open = dict(keys=keys, d_keys=torch.from_numpy(keys.view(np.int16)).to(self.device) if len(keys) else None, cells=cells,
+                          tables=[torch.zeros((npairs if self.per_pair else 1, cells), dtype=torch.int64, device=self.device)] if npairs else [],
+                          npairs=0)
+
+    def _slice(self):
+        o = self._open
+        if not self.per_pair:
+            if not o['tables']:
+                o['tables'].append(torch.zeros((1, o['cells']), dtype=torch.int64, device=self.device))
+            return o['tables'][0][0]
+        rows = sum(int(t.shape[0]) for t in o['tables'])
+        if o['npairs'] >= rows:                          # pairs added one by one: rows in blocks, still one download per video
+            o['tables'].append(torch.zeros((16, o['cells']), dtype=torch.int64, device=self.device))
+            rows += 16
+        i = o['npairs']
+        for t in o['tables']:
+            if i < t.shape[0]:
+                return t[i]
+            i -= int(t.shape[0])
+
+    def add_pair(self, prev, cur, flow, keys=None, flicker=None):
+        """count one pair into the open video (opened by the first pair; `keys` then fixes the video's list, None = the thing keys of
+        these two maps). flicker: None or a device uint8 [H,W] tensor that receives the inconsistency map. Nothing is downloaded."""
+        prev, cur = self._map(prev), self._map(cur)
+        flow, ld = self._flow(flow)
+        H, W = int(cur.shape[0]), int(cur.shape[1])
+        if tuple(prev.shape) != tuple(cur.shape) or (int(flow.shape[0]), int(flow.shape[1])) != (H, W):
+            raise ValueError('maps and flow must have equal H, W: prev %s, cur %s, flow %s' % (tuple(prev.shape), tuple(cur.shape), tuple(flow.shape)))
+        if flicker is not None and not (torch.is_tensor(flicker) and flicker.is_cuda and flicker.dtype == torch.uint8 and flicker.is_contiguous()
+                                        and tuple(flicker.shape) == (H, W)):
+            raise ValueError('flicker is a contiguous device uint8 [H,W] tensor')
+        if self._open is None:
+            self._begin(self.video_keys([prev, cur]) if keys is None else keys, 0)
+        elif keys is not None and not np.array_equal(np.unique(np.asarray(keys)), self._open['keys']):
+            raise ValueError('the keys of a video are fixed by its first pair')
+        o, C = self._open, self.num_classes
+        n = len(o['keys'])
+        conf, psz, csz, same, misc = torch.split(self._slice(), table_sizes(C, n))
+        hip.check(self.lib.vps_tc_accumulate(hip.ptr(prev), hip.ptr(cur), H, W, hip.ptr(flow), ld, 0, self.id_channel,
+                                             self.seg_class.ctypes.data_as(ctypes.c_void_p), C, hip.ptr(o['d_keys']) if n else None, n, hip.ptr(conf),
+                                             hip.ptr(psz) if n else None, hip.ptr(csz) if n else None, hip.ptr(same) if n else None, hip.ptr(misc),
+                                             hip.ptr(flicker), hip.stream_ptr()), 'vps_tc_accumulate')
+        o['npairs'] += 1
+
+    def end_video(self, video_id=None):
+        """the one download (and synchronisation) of the open video; returns its entry (`tc_from_tables` of its tables and the tables)"""
+        o, C = self._open, self.num_classes
+        assert o is not None, 'no video is open'
+        self._open = None
+        host = np.zeros((0, o['cells']), dtype=np.int64)
+        if o['tables']:
+            host = (torch.cat(o['tables']) if len(o['tables']) > 1 else o['tables'][0]).cpu().numpy()
+        host = host[:o['npairs'] if self.per_pair else 1]
+        pairs = host if self.per_pair else None
+        total = host.sum(0)
+        conf, psz, csz, same, misc = np.split(total, np.cumsum(table_sizes(C, len(o['keys'])))[:-1])
+        return self.add_tables(video_id, o['keys'], conf, psz, csz, same, misc, pairs)
+
+    def add_video(self, maps, flows, video_id=None, keys=None, flickers=None):
+        """maps: the unified maps of one video in order, uint8 [H,W,3] host arrays or device tensors; flows: one per map, flows[t] the
+        flow of frame t to frame t-1, fp32 [H,W,2] (flows[0] is not used and may be None); flickers: None or one device uint8 [H,W]
+        tensor (or None) per map. Returns the video's entry."""
+        assert self._open is None, 'a video opened by add_pair is not ended'
+        if len(flows) != len(maps):
+            raise ValueError('one flow per map (the first is not used): %d maps, %d flows' % (len(maps), len(flows)))
+        maps = [self._map(m) for m in maps]
+        self._begin(self.video_keys(maps) if keys is None else keys, max(len(maps) - 1, 0))
+        for t in range(1, len(maps)):                    # no synchronisation between pairs
+            self.add_pair(maps[t - 1], maps[t], flows[t], flicker=None if flickers is None else flickers[t])
+        return self.end_video(video_id)
+
+    def result(self):
+        assert self._open is None, 'a video opened by add_pair is not ended'
+        return super().result()
+
+
+def score_videos(evaluator, maps, flows, names, nframes_per_video, map_dir=None, frames=None, alpha=128, quality=90, entropy='host'):
+    """What `--tc` of the tools does with a run's unified maps (host or device, videos one after the other, `nframes_per_video` each) and
+    the flows kept for them (`flows[i]` = `pano_results['flow']` of frame i): every video through `add_pair`, one download per video.
+    `flows` is EMPTIED as it goes - entry i is set to None once its pair is counted (a video's first frame at once), so each flow
+    lives on the device only until then. map_dir (`--tc-map`): the inconsistency map of every pair, painted with `FLICKER_PALETTE`,
+    blended over `frames[i]` (BGR uint8 [H,W,3]) by `render_overlay` and written as map_dir/<name>.jpg by a `DeviceJpegWriter`.
+    Returns the written file names."""
+    from .postprocess import DeviceJpegWriter, overlay_name, render_overlay, video_name_of
+    assert len(maps) == len(flows) == len(names) and (map_dir is None or (frames is not None and len(frames) == len(maps)))
+    writer = DeviceJpegWriter(evaluator.device, quality=quality, entropy=entropy) if map_dir is not None else None
+    out = []
+    try:
+        for v0 in range(0, len(maps), nframes_per_video):
+            vm = [evaluator._map(m) for m in maps[v0:v0 + nframes_per_video]]
+            keys = evaluator.video_keys(vm)
+            flows[v0] = None
+            for j in range(1, len(vm)):
+                fl = torch.empty(vm[j].shape[:2], dtype=torch.uint8, device=evaluator.device) if writer is not None else None
+                evaluator.add_pair(vm[j - 1], vm[j], flows[v0 + j], keys=keys, flicker=fl)
+                flows[v0 + j] = None
+                if writer is not None:
+                    out.append(overlay_name(map_dir, names[v0 + j]))
+                    writer.submit(render_overlay(frames[v0 + j], flicker_colour(fl), alpha), out[-1])
+            if len(vm) > 1:
+                evaluator.end_video(video_name_of(names[v0:v0 + nframes_per_video], v0 // nframes_per_video))
+    finally:
+        if writer is not None:
+            writer.close()
+    return out
+
+
+def write_outputs(result, out_dir):
+    """tc.txt and tc-tracks.json in `out_dir`"""
+    import json
+    import os
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, 'tc.txt'), 'w') as f:
+        f.write(tc_text(result))
+    with open(os.path.join(out_dir, 'tc-tracks.json'), 'w') as f:
+        json.dump(tc_tracks_json(result), f, indent=1)
