@@ -686,6 +686,43 @@ int vps_tc_accumulate(const uint8_t* prev, const uint8_t* cur, int H, int W, con
                       const uint8_t* seg_class, int num_classes, const uint16_t* keys, int nkeys, int64_t* conf, int64_t* prev_size,
                       int64_t* cur_size, int64_t* same, int64_t* misc, uint8_t* flicker, void* stream);
 
+/* Occlusion-aware temporal consistency (csrc/flow_occ_ops.hip, csrc/tc_ops.hip, vps_amd/tc.py): the forward-backward
+ * flow check (restated from memory of Sundaram et al., ECCV 2010, as used by UnFlow, Meister et al., AAAI 2018; alpha = 0.01, beta = 0.5
+ * there) and the counting pass that honours its mask. One launch each on `stream`; neither synchronises, allocates or zeroes.
+ * vps_flow_occlusion:
+ *   fwd          DEVICE fp32 NHWC flow on the grid of cur, pointing into prev (vps_tc_accumulate's `flow`): pixel p at
+ *                fwd[p * fwd_ld + fwd_coff] (x) and [.. + 1] (y)
+ *   back         DEVICE fp32 NHWC flow on the grid of prev, pointing into cur (FlowNet2 run with the two images swapped), its own
+ *                back_ld and back_coff. Both flows: any 4-byte aligned base; fwd is read as 16-byte loads when it is the dense [h,w,2]
+ *                copy on a 16-byte boundary, either flow as 8-byte loads when its ld is even and base + coff is 8-byte aligned
+ *   occ          NULL, or DEVICE uint8 [H][W], any byte alignment, every byte written: 0 visible, 1 occluded, 2 not in view
+ *   counts       NULL, or DEVICE int64 [3], 8-byte aligned: the call ADDS the number of pixels of each code. Not both NULL.
+ * Per pixel p = (x, y), everything fp32 and every operation rounded on its own (no contraction), in this order:
+ *   u, v = fwd(p); sx = float(x) + u, sy = float(y) + v
+ *   in view: vps_tc_accumulate's rule - qx = floorf(sx + 0.5f), qy likewise, 0 <= qx <= W-1 and 0 <= qy <= H-1 compared as floats before
+ *   any conversion to int (NaN, +-inf, 1e30 fall out). Not in view: code 2, counts[2] += 1, back is not read
+ *   x0 = floorf(sx), wx = sx - x0, x1 = x0 + 1; x0 and x1 are clamped to [0, W-1] after conversion to int; the same for y
+ *   b00 at (y0, x0), b01 at (y0, x1), b10 at (y1, x0), b11 at (y1, x1), per channel: top = b00 + wx*(b01 - b00),
+ *   bot = b10 + wx*(b11 - b10), bt = top + wy*(bot - top)
+ *   dx = u + bt_u, dy = v + bt_v; d2 = dx*dx + dy*dy; m = (u*u + v*v) + (bt_u*bt_u + bt_v*bt_v); thr = alpha*m + beta
+ *   visible (code 0, counts[0]) iff d2 <= thr is true, otherwise occluded (code 1, counts[1]): a NaN anywhere gives occluded
+ * No index is formed from a float before the in-view test has passed and every address of back is clamped, so no flow value makes the
+ * call read outside the two maps. Errors before any launch: -1001 fwd or back NULL, or occ and counts both NULL; -1002 H or W < 1 or
+ * H W >= 2^31; -1003 coff < 0 or ld < coff + 2 for either flow; -1004 counts not 8-byte aligned; -1005 alpha or beta negative or NaN.
+ * vps_tc_accumulate_masked: vps_tc_accumulate with
+ *   mask         DEVICE uint8 [H][W], any byte alignment (vps_flow_occlusion's occ: 0 = count the pixel)
+ *   masked       DEVICE int64 [1], 8-byte aligned, ADDED to
+ * A pixel that is not in view counts as outside (misc[1], flicker 3) whatever its mask byte says; an in-view pixel with mask[p] != 0 adds 1
+ * to masked[0] and to nothing else (flicker 4); an in-view pixel with mask[p] == 0 is counted as vps_tc_accumulate counts it. So
+ * misc[0] + misc[1] + masked[0] grows by H W per call. The table path is chosen by (C+1)^2 + 3 nkeys + 3 cells against
+ * vps_stq_lds_cells(). Errors: those of vps_tc_accumulate; -1001 also for mask or masked NULL, -1006 also for masked. */
+int vps_flow_occlusion(const float* fwd, int fwd_ld, int fwd_coff, const float* back, int back_ld, int back_coff, int H, int W, float alpha,
+                       float beta, uint8_t* occ, int64_t* counts, void* stream);
+int vps_tc_accumulate_masked(const uint8_t* prev, const uint8_t* cur, int H, int W, const float* flow, int flow_ld, int flow_coff, int id_channel,
+                             const uint8_t* seg_class, int num_classes, const uint16_t* keys, int nkeys, int64_t* conf, int64_t* prev_size,
+                             int64_t* cur_size, int64_t* same, int64_t* misc, uint8_t* flicker, const uint8_t* mask, int64_t* masked,
+                             void* stream);
+
 /* Boundary PQ / boundary VPQ (csrc/boundary_ops.hip, vps_amd/boundary.py): the boundary band of EVERY segment of a
  * panoptic map in one call, the device form of Boundary IoU's mask_to_boundary (Cheng et al., CVPR 2021) applied per segment.
  *   pan_rgb   DEVICE uint8 [H][W][3] panoptic map (segment id = R + 256 G + 65536 B, the maps vps_pair_count reads); any byte alignment,

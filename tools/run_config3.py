@@ -79,6 +79,10 @@ def parse_args(argv=None):
                     'on the device until the maps are unified and its pair is counted, 16.8 MB per frame at 1024x2048; off by default)')
     ap.add_argument('--tc-map', default=None, metavar='DIR', help='--tc: write DIR/<name>.jpg for every frame but a video\'s first, the inconsistency map '
                     'blended over the frame (red: class differs, amber: track differs, blue: not in view); keeps the decoded frames like --overlay')
+    ap.add_argument('--tc-occlusion', action='store_true', help='--tc with a forward-backward flow check, also with --video and --tc-map: a second FlowNet2 '
+                    'pass behind every frame gives the flow from the previous frame to this one (another 16.8 MB per frame at 1024x2048 until its pair is '
+                    'counted); pixels where the two flows do not cancel (disocclusions) are left out of the counts and reported as the occluded share '
+                    '(OCC in tc.txt, grey in the --tc-map images; off by default)')
     ap.add_argument('--dry-run', action='store_true')
     ap.add_argument('--dry-size', default='128x256'); ap.add_argument('--dry-videos', type=int, default=1); ap.add_argument('--dry-frames', type=int, default=16)
     ap.add_argument('--check-only', action='store_true')
@@ -212,7 +216,7 @@ def run(args, tmp):
     prep = DeviceImagePrep(**cfg.img_norm_cfg, size_divisor=32, img_scale=(2048, 1024), device=dev)
     files = [os.path.join(img_prefix, x['file_name']) for x in info]
     keep = bool(args.overlay or args.overlay_video or args.tc_map)
-    with_tc = bool(args.tc or args.tc_map)
+    with_tc = bool(args.tc or args.tc_map or args.tc_occlusion)
     if reader is not None:
         assert len(reader) > 0, '%s holds no complete frame' % args.video
         feeder = ClipFeeder(reader, prep, workers=args.png_workers, keep_frames=keep, y4m_matrix=args.video_matrix).start()
@@ -227,6 +231,8 @@ def run(args, tmp):
     if with_tc:
         model.keep_flow = True
         res['all_flows'] = []
+    if args.tc_occlusion:
+        res['all_back_flows'] = []
     t0 = time.perf_counter()
     with torch.no_grad():
         for idx, im in enumerate(info):
@@ -249,6 +255,8 @@ def run(args, tmp):
                 flow_writer.submit(result[2]['flow'], flow_name(args.flow, files[idx], args.flow_format))
             if with_tc:
                 res['all_flows'].append(result[2]['flow'])
+            if args.tc_occlusion:                            # the flow from the previous frame to this one: a second FlowNet2 pass, behind the frame
+                res['all_back_flows'].append(model.flow_between(ref, img, img_shape=meta['img_shape']) if idx % span > 0 else None)
     torch.cuda.synchronize()
     if flow_writer is not None:
         flow_files = flow_writer.close()
@@ -290,17 +298,26 @@ def run(args, tmp):
         nseg = 19                                           # PanopticUnifier(dev, 19, 9): the 19 classes are their own indices, the rest is void
         seg_class = np.full(256, 255, dtype=np.uint8)
         seg_class[:nseg] = np.arange(nseg)
-        ev = tc.TcEvaluator(seg_class, nseg, id_channel=2, device=dev, per_pair=True, id_last_stuff=unifier.id_last_stuff)
+        okw = {}
+        if args.tc_occlusion:
+            ev = tc.TcEvaluator(seg_class, nseg, id_channel=2, device=dev, per_pair=True, id_last_stuff=unifier.id_last_stuff, occlusion=True)
+        else:
+            ev = tc.TcEvaluator(seg_class, nseg, id_channel=2, device=dev, per_pair=True, id_last_stuff=unifier.id_last_stuff)
         order = sorted(range(len(res['all_names'])), key=lambda i: res['all_names'][i])                # the order of pred_pans_2ch
         flows = [res['all_flows'][i] for i in order]
         res['all_flows'] = None                             # `flows` holds them now and lets each one go once its pair is counted
+        if args.tc_occlusion:
+            okw['back_flows'] = [res['all_back_flows'][i] for i in order]
+            res['all_back_flows'] = None
         tfiles = tc.score_videos(ev, pred_pans_2ch, flows, [res['all_names'][i] for i in order], span, map_dir=args.tc_map,
                                  frames=[res['all_frames'][i] for i in order] if args.tc_map else None, alpha=args.overlay_alpha,
-                                 quality=args.overlay_quality, entropy=args.jpeg_entropy)
+                                 quality=args.overlay_quality, entropy=args.jpeg_entropy, **okw)
         r = ev.result()
         tc.write_outputs(r, output_dir)
         report['tc'] = dict(tc=round(100 * r['tc'], 4), tc_sem=round(100 * r['tc_sem'], 4), tc_track=round(100 * r['tc_track'], 4), tracks=r['n_tracks'],
                             in_view_share=round(r['in_view_share'], 6), pairs=len(r['per_pair']), map_files=len(tfiles), file=os.path.join(output_dir, 'tc.txt'))
+        if 'occluded_share' in r:
+            report['tc']['occluded_share'] = round(r['occluded_share'], 6)
         print('TC %.4f  TC_sem %.4f  TC_track %.4f' % (100 * r['tc'], 100 * r['tc_sem'], 100 * r['tc_track']))
     if keep and (args.overlay or args.overlay_video):
         from run_vps_synthetic import ColorGenerator

@@ -54,10 +54,12 @@ def uint8_frame(H, W, seed, shift):
     return synth.synth_frame(H, W, seed=seed, shift=shift, noise=2.0 if shift != (0, 0) else 0.0).astype(np.uint8)
 
 
-def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg_entropy='host', keep_flows=False):
+def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg_entropy='host', keep_flows=False, back_flows=False):
     """test_vpq.py:129-149 + single_gpu_test (:28-69) on `videos` synthetic clips -> pano_results with DEVICE maps.
     `flow` = (directory, format, max_rad): the FlowNet2 flow of EVERY frame as DIR/<name>.<format> (flowvis.FlowWriter).
-    `keep_flows` (--tc): the device flow of every frame in res['all_flows'], 8 bytes per pixel and frame until `tc` has counted its pair"""
+    `keep_flows` (--tc): the device flow of every frame in res['all_flows'], 8 bytes per pixel and frame until `tc` has counted its pair.
+    `back_flows` (--tc-occlusion): after every frame but a video's first, `model.flow_between(ref, img)` - the flow from the previous
+    frame to this one, a second FlowNet2 pass - in res['all_back_flows'] (None for a first frame), the same 8 bytes again"""
     import vps_amd
     from vps_amd import nhwc, synth
     from vps_amd.pipeline import DeviceImagePrep, PairFeeder
@@ -82,6 +84,8 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg
     if keep_flows:
         model.keep_flow = True
         res['all_flows'] = []
+    if back_flows:
+        res['all_back_flows'] = []
     decoded = [[uint8_frame(H, W, seed=v, shift=(2 * f, f)) for f in range(nframes)] for v in range(videos)]   # "cv2.imread" results (BGR uint8)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -104,6 +108,8 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg
                 flow_writer.submit(result[2]['flow'], flow_name(flow[0], name, flow[1]))
             if keep_flows:
                 res['all_flows'].append(result[2]['flow'])
+            if back_flows:
+                res['all_back_flows'].append(model.flow_between(ref, img, img_shape=meta['img_shape']) if f > 0 else None)
     if flow_writer is not None:
         res['flow_files'] = flow_writer.close()
     torch.cuda.synchronize()
@@ -119,7 +125,7 @@ def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_pn
     the same overlays as one Y4M stream per video (y4m.Y4mWriter), beside the JPEGs or, without `overlay`, instead of them; its
     'files' entry receives the streams' names. `tc` = dict(map_dir, alpha, quality): the temporal consistency of EVERY video's consecutive
     frames from res['all_flows'] (vps_amd.tc; tc.txt and tc-tracks.json beside pred.json, the inconsistency overlays in map_dir if it
-    is given); its 'result' entry receives the figures"""
+    is given; with 'occlusion' the forward-backward check on res['all_back_flows'] first); its 'result' entry receives the figures"""
     from vps_amd.postprocess import DevicePngWriter, PanopticUnifier, inference_panoptic_video, write_overlays
     unifier = PanopticUnifier(dev, 19, 9)
     two = unifier.get_unified_pan_result(res['all_ssegs'], res['all_panos'], res['all_pano_cls_inds'], obj_ids=res['all_pano_obj_ids'],
@@ -159,16 +165,23 @@ def tc_score(maps, res, names, nframes_per_video, dev, out_dir, id_last_stuff, o
     from vps_amd import tc
     seg_class = np.full(256, 255, dtype=np.uint8)
     seg_class[:len(CATEGORIES)] = np.arange(len(CATEGORIES))
-    ev = tc.TcEvaluator(seg_class, len(CATEGORIES), id_channel=2, device=dev, per_pair=True, id_last_stuff=id_last_stuff)
+    kw = {}
+    if opt.get('occlusion'):                              # --tc-occlusion: occluded pixels are left out of the counts
+        ev = tc.TcEvaluator(seg_class, len(CATEGORIES), id_channel=2, device=dev, per_pair=True, id_last_stuff=id_last_stuff, occlusion=True)
+    else:
+        ev = tc.TcEvaluator(seg_class, len(CATEGORIES), id_channel=2, device=dev, per_pair=True, id_last_stuff=id_last_stuff)
     at = {n: i for i, n in enumerate(res['all_names'])}
     flows = [res['all_flows'][at[n]] for n in names]
     res['all_flows'] = None                               # `flows` holds them now and lets each one go once its pair is counted
+    if opt.get('occlusion'):
+        kw['back_flows'] = [res['all_back_flows'][at[n]] for n in names]
+        res['all_back_flows'] = None
     frames = None
     if opt.get('map_dir'):
         frames = [np.pad(res['all_frames'][at[n]], ((0, m.shape[0] - res['all_frames'][at[n]].shape[0]), (0, m.shape[1] - res['all_frames'][at[n]].shape[1]),
                                                      (0, 0)), mode='edge') for n, m in zip(names, maps)]
     files = tc.score_videos(ev, maps, flows, names, nframes_per_video, map_dir=opt.get('map_dir'), frames=frames, alpha=opt.get('alpha', 128),
-                            quality=opt.get('quality', 90), entropy=jpeg_entropy)
+                            quality=opt.get('quality', 90), entropy=jpeg_entropy, **kw)
     result = ev.result()
     tc.write_outputs(result, out_dir)
     result['map_files'] = files
@@ -254,6 +267,9 @@ def parse_args(argv=None):
                     'off by default)')
     ap.add_argument('--tc-map', default=None, metavar='DIR', help='--tc: write DIR/<name>.jpg for every frame but a video\'s first, the inconsistency map '
                     'blended over the frame (red: class differs, amber: track differs, blue: not in view)')
+    ap.add_argument('--tc-occlusion', action='store_true', help='--tc with a forward-backward flow check: a second FlowNet2 pass per frame gives the flow from '
+                    'the previous frame to this one, pixels where the two flows do not cancel (disocclusions) are left out of the counts and reported '
+                    'as the occluded share (OCC in pred/tc.txt; grey in the --tc-map images; off by default)')
     return ap.parse_args(argv)
 
 
@@ -265,8 +281,11 @@ def main(argv=None):
     overlay_video = dict(file=args.overlay_video, sampling=args.overlay_video_sampling, files=[], alpha=args.overlay_alpha) if args.overlay_video else None
     nper = len(range(labeled_fid // lambda_, args.frames, lambda_))
     flow = (args.flow, args.flow_format, args.flow_max_rad) if args.flow else None
-    tc = dict(map_dir=args.tc_map, alpha=args.overlay_alpha, quality=args.overlay_quality) if (args.tc or args.tc_map) else None
-    res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated, flow, args.jpeg_entropy, keep_flows=tc is not None)
+    tc = dict(map_dir=args.tc_map, alpha=args.overlay_alpha, quality=args.overlay_quality) if (args.tc or args.tc_map or args.tc_occlusion) else None
+    if tc and args.tc_occlusion:
+        tc['occlusion'] = True
+    res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated, flow, args.jpeg_entropy, keep_flows=tc is not None,
+                        back_flows=args.tc_occlusion)
     t0 = time.perf_counter()
     names, pans, pj = postprocess(res, os.path.join(args.out, 'pred'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png, overlay, args.tubes,
                                   args.jpeg_entropy, overlay_video, tc)
@@ -302,6 +321,8 @@ def main(argv=None):
         r = tc['result']
         report['tc'] = dict(tc=round(100 * r['tc'], 4), tc_sem=round(100 * r['tc_sem'], 4), tc_track=round(100 * r['tc_track'], 4), tracks=r['n_tracks'],
                             in_view_share=round(r['in_view_share'], 6), pairs=len(r['per_pair']), map_files=len(r['map_files']))
+        if 'occluded_share' in r:
+            report['tc']['occluded_share'] = round(r['occluded_share'], 6)
         print('TC %.4f  TC_sem %.4f  TC_track %.4f' % (100 * r['tc'], 100 * r['tc_sem'], 100 * r['tc_track']))
     if overlay_video:                                   # a key of its own: without the option the report is what it was
         report['overlay_video'] = dict(files=overlay_video['files'], sampling=args.overlay_video_sampling)

@@ -3,6 +3,8 @@
 //                          pairs are ADDED to the caller's int64 tables - the class confusion matrix, the sizes of the listed tracks in
 //                          both maps and their agreement, the in-view / outside counts. Optionally one byte per pixel says how the
 //                          pixel disagrees. The tables stay on the device; nothing is zeroed, downloaded or synchronised here.
+//   vps_tc_accumulate_masked   the same with a byte mask (vps_flow_occlusion's): an in-view pixel whose mask byte is not 0 is counted in
+//                          one extra cell and in nothing else
 // Integer adds only: the result does not depend on their order, so two runs (and the two table paths) give identical tables.
 #include "common.h"
 #include <string.h>
@@ -13,7 +15,7 @@ constexpr int TC_THREADS = 256;
 constexpr int TC_PIX = 4;                             // pixels of cur per lane and step: 12 bytes = 3 dwords of the map, 4 bytes of the output
 
 struct TcClasses { uint32_t w[64]; };                 // seg_class[256], handed over in the kernel arguments
-struct TcTables { unsigned long long *conf, *prev_size, *cur_size, *same, *misc; };
+struct TcTables { unsigned long long *conf, *prev_size, *cur_size, *same, *misc, *masked; };   // masked: the MASKED instances only
 
 __device__ __forceinline__ int tc_key_index(const uint16_t* __restrict__ keys, int n, uint32_t v) {
     int lo = 0, hi = n - 1;
@@ -79,15 +81,18 @@ __device__ __forceinline__ void tc_add(const TcCells& c, uint32_t n, uint32_t* t
 // outside counts stay in registers until the end. LDS = true: the adds go to the workgroup's own uint32 image (conf | prev_size |
 // cur_size | same | misc) and leave as one 64-bit atomic per non-zero cell; LDS = false: 64-bit global atomics per run. No workgroup
 // reads what another one writes.
-template <bool LDS>
+// MASKED: `mask` holds one byte per pixel of cur. An in-view pixel whose byte is not 0 is counted in t.masked (the cell behind misc in
+// the LDS image) and in nothing else, its code is 4; the masked flag is part of a run's state, so such a pixel ends the run in front of
+// it and joins none. A pixel that is not in view counts as outside whatever its byte says. MASKED = false is the kernel as it was.
+template <bool LDS, bool MASKED>
 __global__ __launch_bounds__(TC_THREADS)
 void tc_accumulate_kernel(const uint8_t* __restrict__ prev, const uint8_t* __restrict__ cur, int H, int W, const float* __restrict__ flow, int ld,
                           int coff, int fmode, int idch, TcClasses sc, int C, const uint16_t* __restrict__ keys, int nkeys, TcTables t,
-                          uint8_t* __restrict__ flick) {
+                          uint8_t* __restrict__ flick, const uint8_t* __restrict__ mask) {
     extern __shared__ __attribute__((aligned(16))) uint32_t tc_lds[];
     const uint8_t* cls = reinterpret_cast<const uint8_t*>(tc_lds);             // 256 bytes in front of the tables
     uint32_t* tab = tc_lds + 64;
-    const int C1 = C + 1, o_prev = C1 * C1, o_cur = o_prev + nkeys, o_same = o_cur + nkeys, o_misc = o_same + nkeys, cells = o_misc + 2;
+    const int C1 = C + 1, o_prev = C1 * C1, o_cur = o_prev + nkeys, o_same = o_cur + nkeys, o_misc = o_same + nkeys, cells = o_misc + (MASKED ? 3 : 2);
     if (threadIdx.x < 64) tc_lds[threadIdx.x] = sc.w[threadIdx.x];
     if (LDS)
         for (int i = threadIdx.x; i < cells; i += TC_THREADS) tab[i] = 0;
@@ -97,11 +102,12 @@ void tc_accumulate_kernel(const uint8_t* __restrict__ prev, const uint8_t* __res
     const float xmax = (float)(W - 1), ymax = (float)(H - 1);
     const int sh = 8 * idch;
     const bool flick4 = flick && ((uintptr_t)flick & 3) == 0;
-    uint32_t n_in = 0, n_out = 0;
+    const bool mask4 = MASKED && ((uintptr_t)mask & 3) == 0;
+    uint32_t n_in = 0, n_out = 0, n_msk = 0;
     for (long ch0 = (long)blockIdx.x * TC_THREADS; ch0 < nchunk; ch0 += (long)gridDim.x * TC_THREADS) {       // uniform per workgroup
         const long ch = ch0 + threadIdx.x;
         uint32_t run_st = 0, run_len = 0, code = 0;
-        bool run_in = false;
+        bool run_in = false, run_msk = false;
         TcCells cell = {-1, -1, -1, -1};
         if (ch < nchunk) {
             const long p0 = TC_PIX * ch;
@@ -123,6 +129,14 @@ void tc_accumulate_kernel(const uint8_t* __restrict__ prev, const uint8_t* __res
                     }
                 }
             }
+            uint32_t M = 0;                           // the chunk's mask bytes
+            if (MASKED) {
+                if (mask4 && n == TC_PIX) {
+                    M = *reinterpret_cast<const uint32_t*>(mask + p0);
+                } else {
+                    for (int i = 0; i < n; ++i) M |= (uint32_t)mask[p0 + i] << (8 * i);
+                }
+            }
             int y = (int)(p0 / W), x = (int)(p0 - (long)y * W);
             uint32_t codes = 0;
 #pragma unroll
@@ -137,18 +151,23 @@ void tc_accumulate_kernel(const uint8_t* __restrict__ prev, const uint8_t* __res
                     ix = (int)qx; iy = (int)qy;
                     in = ix < W && iy < H;            // (float)(W - 1) is W itself for some W above 2^24: never read past the map
                 }
+                const bool msk = MASKED && in && ((M >> (8 * i)) & 0xffu) != 0;
+                if (msk) in = false;                  // from here on: in = in view and counted
                 uint32_t st = 0;
                 if (in) {
                     const uint8_t* b = prev + 3 * ((long)iy * W + ix);
                     st = (((A[i] & 0xffu) << 8) | ((A[i] >> sh) & 0xffu)) | ((uint32_t)b[0] << 24) | ((uint32_t)b[idch] << 16);
                     ++n_in;
+                } else if (msk) {
+                    ++n_msk;
                 } else {
                     ++n_out;
                 }
-                if (!run_len || in != run_in || st != run_st) {
+                if (!run_len || in != run_in || st != run_st || (MASKED && msk != run_msk)) {
                     if (run_len && run_in) tc_add<LDS>(cell, run_len, tab, o_prev, o_cur, o_same, t);
                     run_in = in; run_st = st; run_len = 0;
-                    code = 3;
+                    if (MASKED) run_msk = msk;
+                    code = msk ? 4 : 3;
                     if (in) {                         // ---- the definition's per-pixel rules, once per run
                         const uint32_t ak = st & 0xffffu, bk = st >> 16;
                         int ca = cls[ak >> 8], cb = cls[bk >> 8];
@@ -192,14 +211,17 @@ void tc_accumulate_kernel(const uint8_t* __restrict__ prev, const uint8_t* __res
     for (int off = 32; off >= 1; off >>= 1) {
         n_in += __shfl_xor(n_in, off, 64);
         n_out += __shfl_xor(n_out, off, 64);
+        if (MASKED) n_msk += __shfl_xor(n_msk, off, 64);
     }
     if (lane == 0) {
         if (LDS) {
             if (n_in) atomicAdd(&tab[o_misc], n_in);
             if (n_out) atomicAdd(&tab[o_misc + 1], n_out);
+            if (MASKED && n_msk) atomicAdd(&tab[o_misc + 2], n_msk);
         } else {
             if (n_in) atomicAdd(&t.misc[0], (unsigned long long)n_in);
             if (n_out) atomicAdd(&t.misc[1], (unsigned long long)n_out);
+            if (MASKED && n_msk) atomicAdd(&t.masked[0], (unsigned long long)n_msk);
         }
     }
     if (LDS) {
@@ -208,7 +230,7 @@ void tc_accumulate_kernel(const uint8_t* __restrict__ prev, const uint8_t* __res
             const uint32_t val = tab[i];
             if (!val) continue;
             unsigned long long* dst = i < o_prev ? t.conf + i : i < o_cur ? t.prev_size + (i - o_prev) : i < o_same ? t.cur_size + (i - o_cur)
-                                    : i < o_misc ? t.same + (i - o_same) : t.misc + (i - o_misc);
+                                    : i < o_misc ? t.same + (i - o_same) : i < o_misc + 2 ? t.misc + (i - o_misc) : t.masked;
             atomicAdd(dst, (unsigned long long)val);
         }
     }
@@ -216,33 +238,50 @@ void tc_accumulate_kernel(const uint8_t* __restrict__ prev, const uint8_t* __res
 
 }  // namespace
 
-extern "C" int vps_tc_accumulate(const uint8_t* prev, const uint8_t* cur, int H, int W, const float* flow, int flow_ld, int flow_coff, int id_channel,
-                                 const uint8_t* seg_class, int num_classes, const uint16_t* keys, int nkeys, int64_t* conf, int64_t* prev_size,
-                                 int64_t* cur_size, int64_t* same, int64_t* misc, uint8_t* flicker, void* stream) {
+// the checks and the launch of both entry points; mask == NULL: the unmasked instances
+static int tc_launch(const uint8_t* prev, const uint8_t* cur, int H, int W, const float* flow, int flow_ld, int flow_coff, int id_channel,
+                     const uint8_t* seg_class, int num_classes, const uint16_t* keys, int nkeys, int64_t* conf, int64_t* prev_size, int64_t* cur_size,
+                     int64_t* same, int64_t* misc, uint8_t* flicker, const uint8_t* mask, int64_t* masked, void* stream) {
     if (!prev || !cur || !flow || !seg_class || !conf || !misc) return VPS_EARG(1);
     if (H < 1 || W < 1 || (long)H * W >= (1L << 31)) return VPS_EARG(2);       // a workgroup's uint32 cells cannot wrap
     if (num_classes < 1 || num_classes > 63) return VPS_EARG(3);
     if (nkeys < 0 || nkeys > 65536) return VPS_EARG(4);
     if (id_channel != 1 && id_channel != 2) return VPS_EARG(5);
     if (nkeys > 0 && (!keys || !prev_size || !cur_size || !same)) return VPS_EARG(1);
-    if (((uintptr_t)conf | (uintptr_t)prev_size | (uintptr_t)cur_size | (uintptr_t)same | (uintptr_t)misc) & 7) return VPS_EARG(6);
+    if (((uintptr_t)conf | (uintptr_t)prev_size | (uintptr_t)cur_size | (uintptr_t)same | (uintptr_t)misc | (uintptr_t)masked) & 7) return VPS_EARG(6);
     if (flow_coff < 0 || flow_ld < flow_coff + 2) return VPS_EARG(7);
     TcTables t = {reinterpret_cast<unsigned long long*>(conf), reinterpret_cast<unsigned long long*>(prev_size),
                   reinterpret_cast<unsigned long long*>(cur_size), reinterpret_cast<unsigned long long*>(same),
-                  reinterpret_cast<unsigned long long*>(misc)};
+                  reinterpret_cast<unsigned long long*>(misc), reinterpret_cast<unsigned long long*>(masked)};
     TcClasses sc;
     memcpy(sc.w, seg_class, 256);                                                // the caller's table may go once the call returns
     const int fmode = (flow_ld == 2 && flow_coff == 0 && ((uintptr_t)flow & 15) == 0) ? 2
                     : ((flow_ld & 1) == 0 && ((uintptr_t)(flow + flow_coff) & 7) == 0) ? 1 : 0;
-    const long cells = (long)(num_classes + 1) * (num_classes + 1) + 3L * nkeys + 2;
+    const long cells = (long)(num_classes + 1) * (num_classes + 1) + 3L * nkeys + (mask ? 3 : 2);
     const long nchunk = ((long)H * W + TC_PIX - 1) / TC_PIX;
     long g = nchunk / (TC_THREADS * 4); if (g > 512) g = 512; if (g < 1) g = 1;            // >= 4 chunks per lane, <= 2 workgroups per CU
     hipStream_t s = (hipStream_t)stream;
-    if (cells <= vps_stq_lds_cells())                                                       // the path depends on the table sizes alone
-        hipLaunchKernelGGL(tc_accumulate_kernel<true>, dim3((unsigned)g), dim3(TC_THREADS), 256 + sizeof(uint32_t) * cells, s, prev, cur, H, W, flow,
-                           flow_ld, flow_coff, fmode, id_channel, sc, num_classes, keys, nkeys, t, flicker);
-    else
-        hipLaunchKernelGGL(tc_accumulate_kernel<false>, dim3((unsigned)g), dim3(TC_THREADS), 256, s, prev, cur, H, W, flow, flow_ld, flow_coff, fmode,
-                           id_channel, sc, num_classes, keys, nkeys, t, flicker);
+    const bool lds = cells <= vps_stq_lds_cells();                                          // the path depends on the table sizes alone
+    const size_t shm = 256 + (lds ? sizeof(uint32_t) * cells : 0);
+    auto kernel = mask ? (lds ? tc_accumulate_kernel<true, true> : tc_accumulate_kernel<false, true>)
+                       : (lds ? tc_accumulate_kernel<true, false> : tc_accumulate_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)g), dim3(TC_THREADS), shm, s, prev, cur, H, W, flow, flow_ld, flow_coff, fmode, id_channel, sc, num_classes,
+                       keys, nkeys, t, flicker, mask);
     return vps_launch_status();
+}
+
+extern "C" int vps_tc_accumulate(const uint8_t* prev, const uint8_t* cur, int H, int W, const float* flow, int flow_ld, int flow_coff, int id_channel,
+                                 const uint8_t* seg_class, int num_classes, const uint16_t* keys, int nkeys, int64_t* conf, int64_t* prev_size,
+                                 int64_t* cur_size, int64_t* same, int64_t* misc, uint8_t* flicker, void* stream) {
+    return tc_launch(prev, cur, H, W, flow, flow_ld, flow_coff, id_channel, seg_class, num_classes, keys, nkeys, conf, prev_size, cur_size, same, misc,
+                     flicker, nullptr, nullptr, stream);
+}
+
+extern "C" int vps_tc_accumulate_masked(const uint8_t* prev, const uint8_t* cur, int H, int W, const float* flow, int flow_ld, int flow_coff,
+                                        int id_channel, const uint8_t* seg_class, int num_classes, const uint16_t* keys, int nkeys, int64_t* conf,
+                                        int64_t* prev_size, int64_t* cur_size, int64_t* same, int64_t* misc, uint8_t* flicker, const uint8_t* mask,
+                                        int64_t* masked, void* stream) {
+    if (!mask || !masked) return VPS_EARG(1);
+    return tc_launch(prev, cur, H, W, flow, flow_ld, flow_coff, id_channel, seg_class, num_classes, keys, nkeys, conf, prev_size, cur_size, same, misc,
+                     flicker, mask, masked, stream);
 }

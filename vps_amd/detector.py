@@ -144,6 +144,7 @@ class PanopticFuseTrack(HipModule):
         self._lane = None
         self._slot = 0
         self._ws = None
+        self._between_ws = None
         self._flip = 0
         self._cache = None
         self._handoff = None
@@ -195,6 +196,33 @@ class PanopticFuseTrack(HipModule):
             Ho, Wo = int(flow.H * scale_factor), int(flow.W * scale_factor)
             flow = nhwc.resize(flow, ws.fmap('flow_s', 1, Ho, Wo, 2), 'bilinear', scale_factor)
         return flow.to_nchw(), None
+
+    @torch.no_grad()
+    def flow_between(self, a, b, img_shape=None):
+        """FlowNet2 on the pair (a, b): NCHW [1,3,H,W] normalised device tensors, as the detector gets them (a list holding one is
+        taken as that one). -> device fp32 [h,w,2], a contiguous copy of the caller's own: the flow on the grid of `a` that points into
+        `b` (b sampled at p + flow(p) lies over a(p)), cropped to img_shape[:2] (a frame's img_meta['img_shape']: without the
+        Pad-to-32 rows) when that is given. `pano_results['flow']` of a frame (`keep_flow`) is flow_between(img, ref_img);
+        flow_between(ref_img, img) is the backward flow of that pair, what the occlusion option of vps_amd.tc needs.
+        Call it after the frame's `model(...)` call. It runs on the current stream, in a workspace and a block pool of its own and
+        under buffer names of its own, so it touches nothing of the detector's schedule: not the prefetch records, not the ring or
+        lane workspaces, not the addresses the main workspace's temporaries get. The price is a second set of FlowNet2 buffers
+        (`workspace_bytes` counts them) and one more FlowNet2 pass per call."""
+        if not self.with_fusion:
+            raise hip.VpsHipError('flow_between: %s computes no optical flow (no FlowNet2 on its path)' % type(self).__name__)
+        a = a[0] if isinstance(a, (list, tuple)) else a
+        b = b[0] if isinstance(b, (list, tuple)) else b
+        if not (a.is_cuda and b.is_cuda):
+            raise hip.VpsHipError('PanopticFuseTrack runs on the device only (no CPU path)')
+        if a.shape != b.shape:
+            raise ValueError('flow_between takes two images of one size, got %s and %s' % (tuple(a.shape), tuple(b.shape)))
+        dev = a.device
+        self.ensure_packed(dev)
+        if self._between_ws is None or self._between_ws.device != dev:
+            self._between_ws = nhwc.Workspace(dev)
+        flow = self.flownet2.run(a, b, self._mean_t, self._std_t, self._between_ws, tag='between.fn2.')
+        h, w = (flow.H, flow.W) if img_shape is None else (int(img_shape[0]), int(img_shape[1]))
+        return flow.t[0, :h, :w, flow.coff:flow.coff + 2].clone(memory_format=torch.contiguous_format)
 
     # ------------------------------------------------------------------------------------------------------
     def forward(self, img, img_meta, return_loss=True, **kwargs):
@@ -550,7 +578,8 @@ class PanopticFuseTrack(HipModule):
         """device bytes held by the detector's workspaces: persistent buffers of the main / lane / ring workspaces + the block pool"""
         if self._ws is None:
             return 0
-        return sum(w.nbytes() for w in [self._ws, self._lane] + self._ring) + self._ws.pool.total
+        between = 0 if self._between_ws is None else self._between_ws.nbytes() + self._between_ws.pool.total
+        return sum(w.nbytes() for w in [self._ws, self._lane] + self._ring) + self._ws.pool.total + between
 
     def _enqueue_image_stages(self, nimg, nref, main, defer_backbone=False, busy=()):
         """The image-only stages (FlowNet2, ResNet + FPN + gather) of a frame go to the prefetch streams: for the frame the NEXT call
