@@ -723,6 +723,44 @@ int vps_tc_accumulate_masked(const uint8_t* prev, const uint8_t* cur, int H, int
                              int64_t* cur_size, int64_t* same, int64_t* misc, uint8_t* flicker, const uint8_t* mask, int64_t* masked,
                              void* stream);
 
+/* Optical-flow accuracy against ground truth (csrc/flow_err_ops.hip, vps_amd/floweval.py): end-point error, outlier
+ * and speed-bin counts and the error image of ONE (pred, gt) pair of flows. The rules are restated from memory of the KITTI, Sintel and
+ * Middlebury kits (vps_amd/floweval.py). Two launches on `stream` (the counting pass, then one workgroup that adds the partial sums); the
+ * call does not synchronise, allocate or zero.
+ *   pred, gt     DEVICE fp32 NHWC flows, pixel p at f[p * ld + coff] (x) and [.. + 1] (y) as vps_flow_colour / vps_tc_accumulate, each with
+ *                its own ld and coff; any 4-byte aligned base. Either is read as 16-byte loads when it is the dense [h,w,2] copy on a
+ *                16-byte boundary, as 8-byte loads when its ld is even and base + coff is 8-byte aligned, as 4-byte loads otherwise
+ *   mask         NULL, or DEVICE uint8 [H][W], any byte alignment (read as aligned dwords, bytewise at the edges): 1 = valid and not
+ *                occluded (group noc = 0), 2 = valid and occluded in the ground truth (group occ = 1), 0 and >= 3 = invalid.
+ *                NULL: every pixel is in group noc
+ *   occ_pred     NULL, or DEVICE uint8 [H][W], any byte alignment: the codes of vps_flow_occlusion (0 visible, 1 occluded, 2 not in view)
+ *   counts       DEVICE int64 [25], 8-byte aligned, ADDED to: [g * 12 + k] for the groups g = 0 (noc), 1 (occ) and cell 24 = invalid pixels.
+ *                k: 0 n (valid, not bad), 1 bad, 2 Fl outliers, 3 / 4 / 5 epe > 1 / 3 / 5, 6 / 7 / 8 n with mag < 10 / 10 <= mag < 40 /
+ *                mag >= 40, 9 / 10 / 11 valid pixels (bad ones too) whose occ_pred code is 0 / 1 / 2 (a code >= 3 is counted in none;
+ *                untouched when occ_pred is NULL). Cells 0 and 1 of both groups and cell 24 together grow by H W per call
+ *   sums         DEVICE double [2][4], 8-byte aligned, ADDED to: per group the sum of epe over n and over each of the three speed bins
+ *   err_rgb      NULL, or DEVICE uint8 [H][W][3], any byte alignment, every byte written in the counting launch
+ *   ws           DEVICE workspace, 8-byte aligned, at least vps_flow_error_ws_bytes(H, W) bytes (HOST arithmetic; -1002 for a bad size):
+ *                eight doubles per workgroup of the counting launch
+ * Per pixel, fp64 from the fp32 inputs, every operation rounded on its own (no contraction):
+ *   invalid      the mask says so, or a gt component is NaN or |.| > 1e9 (unknown flow): counts[24] += 1, nothing else; black
+ *   bad          valid, but a pred component is NaN, +-inf or |.| > 1e9: cell 1 and the occ_pred cell; no sum; (255, 0, 255)
+ *   otherwise    du = u - ug, dv = v - vg, epe = sqrt(du*du + dv*dv), mag = sqrt(ug*ug + vg*vg); outlier iff epe > 3.0 and
+ *                epe > 0.05 * mag (KITTI, strict, a product); colour: n_err = min(epe / 3.0, epe / (0.05 * mag)), epe / 3.0 when
+ *                mag == 0; the first row with n_err < hi of hi = 0.1875, 0.375, 0.75, 1.5, 3, 6, 12, 24, 48, inf ->
+ *                (49,54,149) (69,117,180) (116,173,209) (171,217,233) (224,243,248) (254,224,144) (253,174,97) (244,109,67) (215,48,39)
+ *                (165,0,38)
+ * Determinism: the counts leave a workgroup as one 64-bit integer atomic per non-zero cell; the sums are reduced in a fixed tree inside
+ * the workgroup, written to the workgroup's own slot of ws, and the second launch adds the slots in a fixed order (lane by lane in
+ * ascending slot order, then a fixed tree) before it adds the totals to `sums`: no floating-point atomics, the same bytes on every call.
+ * No address is formed from a flow value. Errors before any launch: -1001 pred, gt, counts, sums or ws NULL; -1002 H or W < 1 or
+ * H W >= 2^31; -1003 coff < 0 or ld < coff + 2 for either flow; -1004 counts or sums not 8-byte aligned, or a flow base not 4-byte
+ * aligned; -1005 ws not 8-byte aligned or ws_bytes too small. */
+int64_t vps_flow_error_ws_bytes(int H, int W);
+int vps_flow_error(const float* pred, int pred_ld, int pred_coff, const float* gt, int gt_ld, int gt_coff, const uint8_t* mask,
+                   const uint8_t* occ_pred, int H, int W, int64_t* counts, double* sums, uint8_t* err_rgb, void* ws, int64_t ws_bytes,
+                   void* stream);
+
 /* Boundary PQ / boundary VPQ (csrc/boundary_ops.hip, vps_amd/boundary.py): the boundary band of EVERY segment of a
  * panoptic map in one call, the device form of Boundary IoU's mask_to_boundary (Cheng et al., CVPR 2021) applied per segment.
  *   pan_rgb   DEVICE uint8 [H][W][3] panoptic map (segment id = R + 256 G + 65536 B, the maps vps_pair_count reads); any byte alignment,
