@@ -96,7 +96,29 @@ kernel on an MI355X)):
   flow_prep         18   6.05e-06 7.63e-06 2.42e-05  3.53e-06  1e-05 + 0 |ref|
   (resize: the large figures belong to alpha = -20, |reference| up to 80; flow_prep: to rgb_mean, values of ~100, cap 1e-4. The two far-mean
   GroupNorm cases are also held to the bound of tests/nn_cases.py groupnorm_affine_bound, 1.9e-2 / 1.4e-2, derived from the number
-  formats: measured 3.7e-5 / 3.9e-5; float32 statistics would be off by whole units.)"""
+  formats: measured 3.7e-5 / 3.9e-5; float32 statistics would be off by whole units.)
+
+Kernel-level tests of the correlation kernels (tests/test_corr_gpu.py against tests/corr_restate.py, cases in tests/corr_cases.py: every
+kernel instance vps_correlation / vps_correlation_f16 launch at their default switch values, N = 2, channel windows, C up to 1024):
+out-of-image displacements compare BITWISE with +0.0, an N = 1 call on image 1 BITWISE with the second half of the N = 2 call, and
+vps_correlation_f16 without a matrix-core instance BITWISE with vps_correlation. Everything else compares with the float64 restatement:
+the exact kernels under the same derived bound = max(floor, 4 x max|float32 restatement - float64 restatement|), floor = one float32 ulp
+of the case's largest |reference|, asserted on the CPU (tests/test_corr_restate.py) not to exceed the cap of tests/test_hip_ops.py,
+1e-5 + 1e-5 max|reference|; the split-fp16 matrix-core kernel under the project's figure for it, 2e-6 max|reference|. Largest figures per
+kernel over its cases (absolute - the cases' output magnitudes differ by orders, hence the last column; per case in CORR_MEASURED
+below as (float32 vs float64, bound used, measured max error of the kernel on an MI355X)):
+
+  kernel                        cases  f32 v f64  floor     bound     kernel    largest kernel / bound of a case
+  correlation_kernel<1>            6   3.81e-04  1.95e-03  1.95e-03  1.94e-04  0.48
+  correlation_kernel<2>            2   2.54e-05  1.53e-05  1.01e-04  1.82e-05  0.30
+  correlation_kernel<4>            3   1.24e-05  7.63e-06  4.95e-05  9.09e-06  0.53
+  correlation4_kernel<2,10,1>      6   1.80e-04  6.10e-05  7.21e-04  1.32e-04  0.27
+  correlation4h_kernel<4,1>        4   4.76e-06  3.81e-06  1.91e-05  2.96e-06  0.27
+  correlation4h_kernel<4,2>        4   5.31e-06  3.81e-06  2.12e-05  6.84e-06  0.34
+  correlation_lds_kernel<2,10>     5   2.48e-05  1.53e-05  9.94e-05  6.47e-05  0.79
+  corr_mfma_kernel<2,10,8>         4   2.96e-05  1.53e-05  4.81e-04  5.93e-05  0.23   (bound: 2e-6 max|reference|)
+  (correlation_lds_kernel sums its channels one after the other in one lane, the restatement pairwise: it comes closest to its bound.
+  The first case of correlation_kernel<1> has four channels, one of them scaled by 80: outputs of 2e4.)"""
 
 STAGE = dict(flow=5e-5, fpn=5e-5, neck=2e-3, fcn_score=2e-3, cls_score=2e-3, bbox_pred=2e-3, score=2e-3)
 STAGE_R101 = dict(neck=1e-2, fcn_score=1e-2, cls_score=1e-2, bbox_pred=1e-2, score=1e-2)      # the stages behind the FPN of the 101-layer model
@@ -228,6 +250,44 @@ NN_OPS_MEASURED = {
         '16x16_64x64_nblk1_ld8': (1.19e-07, 4.77e-07, 1.19e-07), '16x16_64x64_nblk1_ld8:rgb_mean': (4.83e-07, 1.93e-06, 5.98e-08),
         '16x16_64x64_nblk4_ld12': (9.99e-08, 3.99e-07, 9.99e-08), '16x16_64x64_nblk4_ld12:rgb_mean': (1.91e-07, 9.54e-07, 1.91e-07),
         '16x16_64x64_nblk64_ld8': (1.26e-07, 5.05e-07, 1.01e-07), '16x16_64x64_nblk64_ld8:rgb_mean': (2.79e-07, 1.12e-06, 2.79e-07),
+    },
+}
+
+# the same record for tests/test_corr_gpu.py, per kernel instance and case: (max|float32 - float64 restatement|, bound used, max error the kernel showed)
+CORR_MEASURED = {
+    'correlation_kernel<1>': {
+        'f32_N2_5x7_C4_md0_s1_ttt': (0.000381, 0.00195, 0.000194), 'f32_N2_5x7_C12_md3_s1_www_leaky': (1.68e-07, 6.72e-07, 3.23e-07),
+        'f32_N1_9x11_C64_md4_s1_sst': (4.41e-06, 1.76e-05, 3.75e-06), 'f32_N2_12x20_C256_md20_s2_twt_leaky': (1.26e-05, 5.02e-05, 1.1e-05),
+        'f32_N2_7x9_C8_md6_s3_wtw': (5.58e-07, 2.23e-06, 5.58e-07), 'f32_N1_512x516_C4_md1_s1_ttt': (7.3e-06, 2.92e-05, 3.8e-06),
+    },
+    'correlation_kernel<2>': {
+        'f32_N2_4x6_C260_md4_s1_wwt': (2.54e-05, 0.000101, 1.82e-05), 'f32_N1_4x6_C512_md2_s1_ttw_leaky': (5.74e-07, 2.3e-06, 6.95e-07),
+    },
+    'correlation_kernel<4>': {
+        'f32_N2_3x5_C516_md2_s1_ssw': (1.24e-05, 4.95e-05, 9.09e-06), 'f32_N1_3x5_C1024_md4_s1_ttt': (2.68e-06, 1.07e-05, 3.03e-06),
+        'f32_N1_3x5_C772_md1_s1_wtt_leaky': (1.12e-06, 4.47e-06, 2.36e-06),
+    },
+    'correlation4_kernel<2,10,1>': {
+        'f32_N2_5x8_C4_md20_s2_ttt': (5.17e-07, 2.07e-06, 4.04e-07), 'f32_N2_7x24_C128_md20_s2_www': (2.2e-06, 8.79e-06, 2.26e-06),
+        'f32_N1_3x40_C256_md20_s2_sst_leaky': (2.34e-06, 9.35e-06, 2.54e-06), 'f32_N1_4x16_C36_md20_s2_ttw': (2.04e-06, 8.16e-06, 1.2e-06),
+        'f32_N1_2x256_C36_md20_s2_wtt': (3.37e-05, 0.000135, 2.87e-05), 'f16_N1_4x128_C128_md20_s2_ttt': (0.00018, 0.000721, 0.000132),
+    },
+    'correlation4h_kernel<4,1>': {
+        'f32_N2_5x4_C4_md4_s1_ttt': (1.97e-07, 7.87e-07, 1.98e-07), 'f32_N2_9x12_C128_md4_s1_www': (4.76e-06, 1.91e-05, 2.96e-06),
+        'f32_N1_6x8_C100_md4_s1_sst_leaky': (1.8e-06, 7.2e-06, 1.11e-06), 'f32_N2_96x172_C8_md4_s1_ttt': (6.44e-07, 2.57e-06, 6.85e-07),
+    },
+    'correlation4h_kernel<4,2>': {
+        'f32_N2_6x8_C132_md4_s1_ttw': (1.77e-06, 7.09e-06, 1.66e-06), 'f32_N1_10x16_C200_md4_s1_www_leaky': (3.76e-06, 1.51e-05, 2e-06),
+        'f32_N2_4x12_C256_md4_s1_sst': (5.07e-06, 2.03e-05, 6.84e-06), 'f16_N1_4x64_C256_md4_s1_ttw': (5.31e-06, 2.12e-05, 4.23e-06),
+    },
+    'correlation_lds_kernel<2,10>': {
+        'f32_N2_3x256_C32_md20_s2_ttt': (2.48e-05, 9.94e-05, 6.47e-05), 'f32_N2_3x256_C96_md20_s2_ssw': (2.29e-06, 9.14e-06, 7.24e-06),
+        'f32_N1_2x512_C64_md20_s2_wwt_leaky': (3.37e-07, 1.35e-06, 6.93e-07), 'f32_N2_23x256_C32_md20_s2_ttw': (2.62e-06, 1.05e-05, 4.84e-06),
+        'f32_N1_1x256_C32_md20_s2_twt': (8.84e-08, 3.53e-07, 1.75e-07),
+    },
+    'corr_mfma_kernel<2,10,8>': {
+        'f16_N2_3x128_C256_md20_s2_ttt': (2.96e-05, 0.000219, 2.7e-05), 'f16_N2_2x256_C256_md20_s2_www': (5.1e-06, 8.62e-05, 2.01e-05),
+        'f16_N1_1x128_C256_md20_s2_sst': (1.32e-06, 2.01e-05, 1.7e-06), 'f16_N2_3x128_C256_md20_s2_ttw_leaky': (2.74e-05, 0.000481, 5.93e-05),
     },
 }
 
