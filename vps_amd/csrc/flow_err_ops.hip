@@ -9,64 +9,21 @@
 // fused multiply-add under the root decides differently. sqrt and / of doubles are correctly rounded on the device.
 // Determinism: integer atomics for the counts; the sums never meet a floating-point atomic - fixed trees and one slot per workgroup.
 // No address is formed from a flow value: NaN, inf and 1e30 read and write nothing outside the buffers.
-#include "common.h"
+#include "px4.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int FE_THREADS = 256;
-constexpr int FE_PIX = 4;                             // pixels per lane and step: 32 bytes of each flow, 4 of each byte map, 12 of the image
 constexpr int FE_MAX_GROUPS = 1024;                   // workgroups of the counting launch = slots of the workspace (4 per CU, then grid-stride)
 constexpr int FE_CELLS = 25, FE_SUMS = 8;
 constexpr double FE_UNKNOWN = 1e9;                    // the Middlebury convention of vps_flow_max_radius
 
 long fe_groups(long npix) {
-    const long nchunk = (npix + FE_PIX - 1) / FE_PIX;
+    const long nchunk = (npix + PX4 - 1) / PX4;
     long g = (nchunk + FE_THREADS - 1) / FE_THREADS;
     return g > FE_MAX_GROUPS ? FE_MAX_GROUPS : g;
-}
-
-int fe_mode(const float* f, int ld, int coff) {
-    return (ld == 2 && coff == 0 && ((uintptr_t)f & 15) == 0) ? 2 : ((ld & 1) == 0 && ((uintptr_t)(f + coff) & 7) == 0) ? 1 : 0;
-}
-
-// pixels p0 .. p0 + n - 1 of a flow: two 16-byte loads (fmode 2, a whole chunk), one 8-byte load per pixel (fmode 1) or two 4-byte ones
-__device__ __forceinline__ void fe_load_flow(const float* __restrict__ f, int ld, int coff, int fmode, long p0, int n, float (&u)[FE_PIX],
-                                             float (&v)[FE_PIX]) {
-    if (fmode == 2 && n == FE_PIX) {
-        const float4 f0 = *reinterpret_cast<const float4*>(f + 2 * p0), f1 = *reinterpret_cast<const float4*>(f + 2 * p0 + 4);
-        u[0] = f0.x; v[0] = f0.y; u[1] = f0.z; v[1] = f0.w; u[2] = f1.x; v[2] = f1.y; u[3] = f1.z; v[3] = f1.w;
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < FE_PIX; ++i) {
-        u[i] = v[i] = 0.f;
-        if (i < n) {
-            const float* q = f + (p0 + i) * ld + coff;
-            if (fmode >= 1) { const float2 g = *reinterpret_cast<const float2*>(q); u[i] = g.x; v[i] = g.y; }
-            else { u[i] = q[0]; v[i] = q[1]; }
-        }
-    }
-}
-
-// bytes p0 .. p0 + n - 1 of a [npix] byte map whose base need not be dword-aligned (p0 is a multiple of 4), byte i in bits 8 i: one aligned
-// dword, or two aligned dwords shifted into place when the base is off a dword boundary. A chunk whose dwords would reach in front of
-// the base or past byte npix is read byte by byte (tc_ops.hip has the same for its maps).
-__device__ __forceinline__ uint32_t fe_load_bytes(const uint8_t* __restrict__ p, long npix, long p0, int n) {
-    const unsigned o = (unsigned)((uintptr_t)p & 3);
-    if (n == FE_PIX) {
-        if (!o) return *reinterpret_cast<const uint32_t*>(p + p0);
-        if (p0 >= 4 && p0 - (long)o + 8 <= npix) {
-            const uint32_t* w = reinterpret_cast<const uint32_t*>(p + p0 - o);
-            return __builtin_amdgcn_alignbyte(w[1], w[0], o);
-        }
-    }
-    uint32_t r = 0;
-#pragma unroll
-    for (int i = 0; i < FE_PIX; ++i)
-        if (i < n) r |= (uint32_t)p[p0 + i] << (8 * i);
-    return r;
 }
 
 // the row of the error-colour table, R | G << 8 | B << 16
@@ -97,7 +54,7 @@ void flow_error_kernel(const float* __restrict__ pred, int pld, int pcoff, int p
                        double* __restrict__ slots, uint8_t* __restrict__ rgb) {
     __shared__ uint32_t red_c[FE_THREADS / 64][FE_CELLS];
     __shared__ double red_s[FE_THREADS / 64][FE_SUMS];
-    const long nchunk = (npix + FE_PIX - 1) / FE_PIX;
+    const long nchunk = (npix + PX4 - 1) / PX4;
     const bool rgb4 = rgb && ((uintptr_t)rgb & 3) == 0;
     uint32_t cnt[2][12], n_inv = 0;
     double sum[2][4];
@@ -109,16 +66,16 @@ void flow_error_kernel(const float* __restrict__ pred, int pld, int pcoff, int p
         for (int k = 0; k < 4; ++k) sum[g][k] = 0.0;
     }
     for (long ch = (long)blockIdx.x * FE_THREADS + threadIdx.x; ch < nchunk; ch += (long)gridDim.x * FE_THREADS) {
-        const long p0 = FE_PIX * ch;
-        const int n = (int)min((long)FE_PIX, npix - p0);
-        float u[FE_PIX], v[FE_PIX], ug[FE_PIX], vg[FE_PIX];
-        fe_load_flow(pred, pld, pcoff, pmode, p0, n, u, v);
-        fe_load_flow(gt, gld, gcoff, gmode, p0, n, ug, vg);
-        const uint32_t M = mask ? fe_load_bytes(mask, npix, p0, n) : 0x01010101u;
-        const uint32_t O = occ_pred ? fe_load_bytes(occ_pred, npix, p0, n) : 0xffffffffu;
-        uint32_t col[FE_PIX] = {0, 0, 0, 0};
+        const long p0 = PX4 * ch;
+        const int n = (int)min((long)PX4, npix - p0);
+        float u[PX4], v[PX4], ug[PX4], vg[PX4];
+        px4_load_flow(pred, pld, pcoff, pmode, p0, n, u, v);
+        px4_load_flow(gt, gld, gcoff, gmode, p0, n, ug, vg);
+        const uint32_t M = mask ? px4_load_bytes(mask, npix, p0, n) : 0x01010101u;
+        const uint32_t O = occ_pred ? px4_load_bytes(occ_pred, npix, p0, n) : 0xffffffffu;
+        uint32_t col[PX4] = {0, 0, 0, 0};
 #pragma unroll
-        for (int i = 0; i < FE_PIX; ++i) {
+        for (int i = 0; i < PX4; ++i) {
             if (i >= n) break;
             // ---- the definition, in its order
             const double dug = (double)ug[i], dvg = (double)vg[i], du0 = (double)u[i], dv0 = (double)v[i];
@@ -159,37 +116,23 @@ void flow_error_kernel(const float* __restrict__ pred, int pld, int pcoff, int p
                 sum[g][3] += mine && b2 ? epe : 0.0;
             }
         }
-        if (rgb) {
-            uint8_t* q = rgb + 3 * p0;
-            if (rgb4 && n == FE_PIX) {
-                uint32_t* w = reinterpret_cast<uint32_t*>(q);
-                w[0] = col[0] | (col[1] << 24);
-                w[1] = (col[1] >> 8) | (col[2] << 16);
-                w[2] = (col[2] >> 16) | (col[3] << 8);
-            } else {
-#pragma unroll
-                for (int i = 0; i < FE_PIX; ++i)
-                    if (i < n) { q[3 * i] = (uint8_t)col[i]; q[3 * i + 1] = (uint8_t)(col[i] >> 8); q[3 * i + 2] = (uint8_t)(col[i] >> 16); }
-            }
-        }
+        if (rgb) px4_store_px3(rgb, rgb4, p0, n, col);
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
 #pragma unroll
         for (int k = 0; k < 12; ++k) {
-            uint32_t c = cnt[g][k];
-            for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+            const uint32_t c = wave_sum(cnt[g][k]);
             if (lane == 0) red_c[wave][g * 12 + k] = c;
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            double s = sum[g][k];
-            for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);      // s(l) + s(l ^ off): the same tree in every lane
+            const double s = wave_sum(sum[g][k]);                                     // s(l) + s(l ^ off): the same tree in every lane
             if (lane == 0) red_s[wave][g * 4 + k] = s;
         }
     }
-    for (int off = 32; off >= 1; off >>= 1) n_inv += __shfl_xor(n_inv, off, 64);
+    n_inv = wave_sum(n_inv);
     if (lane == 0) red_c[wave][24] = n_inv;
     __syncthreads();
     if (threadIdx.x < FE_CELLS) {
@@ -234,8 +177,8 @@ extern "C" int vps_flow_error(const float* pred, int pred_ld, int pred_coff, con
     const long npix = (long)H * W, g = fe_groups(npix);
     if (((uintptr_t)ws & 7) || ws_bytes < (int64_t)(g * FE_SUMS * sizeof(double))) return VPS_EARG(5);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(flow_error_kernel, dim3((unsigned)g), dim3(FE_THREADS), 0, s, pred, pred_ld, pred_coff, fe_mode(pred, pred_ld, pred_coff), gt,
-                       gt_ld, gt_coff, fe_mode(gt, gt_ld, gt_coff), mask, occ_pred, npix, reinterpret_cast<unsigned long long*>(counts),
+    hipLaunchKernelGGL(flow_error_kernel, dim3((unsigned)g), dim3(FE_THREADS), 0, s, pred, pred_ld, pred_coff, px4_flow_mode(pred, pred_ld, pred_coff), gt,
+                       gt_ld, gt_coff, px4_flow_mode(gt, gt_ld, gt_coff), mask, occ_pred, npix, reinterpret_cast<unsigned long long*>(counts),
                        static_cast<double*>(ws), err_rgb);
     int st = vps_launch_status();
     if (st) return st;

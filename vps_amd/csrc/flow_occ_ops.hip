@@ -7,14 +7,13 @@
 // pixel: d2 <= thr sits on the boundary for whole-pixel shifts against a zero flow, where a fused multiply-add decides differently.
 // No index is formed from a float before the in-view test has passed, and every address of `back` is clamped to the map: NaN, inf and
 // 1e30 flows read nothing outside it.
-#include "common.h"
+#include "px4.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int OCC_THREADS = 256;
-constexpr int OCC_PIX = 4;                            // pixels of cur per lane and step: 32 bytes of fwd, 4 bytes of the mask
 
 __device__ __forceinline__ float2 occ_load2(const float* __restrict__ f, bool pair) {
     if (pair) return *reinterpret_cast<const float2*>(f);
@@ -30,31 +29,19 @@ __global__ __launch_bounds__(OCC_THREADS)
 void flow_occlusion_kernel(const float* __restrict__ fwd, int fld, int fcoff, int fmode, const float* __restrict__ back, int bld, int bcoff,
                            int bpair, int H, int W, float alpha, float beta, uint8_t* __restrict__ occ, unsigned long long* __restrict__ counts) {
     __shared__ uint32_t red[OCC_THREADS / 64][3];
-    const long npix = (long)H * W, nchunk = (npix + OCC_PIX - 1) / OCC_PIX;
+    const long npix = (long)H * W, nchunk = (npix + PX4 - 1) / PX4;
     const float xmax = (float)(W - 1), ymax = (float)(H - 1);
     const bool occ4 = occ && ((uintptr_t)occ & 3) == 0;
     uint32_t cnt[3] = {0, 0, 0};
     for (long ch = (long)blockIdx.x * OCC_THREADS + threadIdx.x; ch < nchunk; ch += (long)gridDim.x * OCC_THREADS) {
-        const long p0 = OCC_PIX * ch;
-        const int n = (int)min((long)OCC_PIX, npix - p0);
-        float u[OCC_PIX], v[OCC_PIX];
-        if (fmode == 2 && n == OCC_PIX) {
-            const float4 f0 = *reinterpret_cast<const float4*>(fwd + 2 * p0), f1 = *reinterpret_cast<const float4*>(fwd + 2 * p0 + 4);
-            u[0] = f0.x; v[0] = f0.y; u[1] = f0.z; v[1] = f0.w; u[2] = f1.x; v[2] = f1.y; u[3] = f1.z; v[3] = f1.w;
-        } else {
-#pragma unroll
-            for (int i = 0; i < OCC_PIX; ++i) {
-                u[i] = v[i] = 0.f;
-                if (i < n) {
-                    const float2 g = occ_load2(fwd + (p0 + i) * fld + fcoff, fmode >= 1);
-                    u[i] = g.x; v[i] = g.y;
-                }
-            }
-        }
+        const long p0 = PX4 * ch;
+        const int n = (int)min((long)PX4, npix - p0);
+        float u[PX4], v[PX4];
+        px4_load_flow(fwd, fld, fcoff, fmode, p0, n, u, v);
         int y = (int)(p0 / W), x = (int)(p0 - (long)y * W);
         uint32_t codes = 0;
 #pragma unroll
-        for (int i = 0; i < OCC_PIX; ++i) {
+        for (int i = 0; i < PX4; ++i) {
             if (i >= n) break;
             // ---- the definition, in its order
             const float sx = (float)x + u[i], sy = (float)y + v[i];
@@ -83,18 +70,11 @@ void flow_occlusion_kernel(const float* __restrict__ fwd, int fld, int fcoff, in
             codes |= code << (8 * i);
             if (++x == W) { x = 0; ++y; }
         }
-        if (occ) {
-            if (occ4 && n == OCC_PIX) {
-                *reinterpret_cast<uint32_t*>(occ + p0) = codes;
-            } else {
-                for (int i = 0; i < n; ++i) occ[p0 + i] = (uint8_t)(codes >> (8 * i));
-            }
-        }
+        if (occ) px4_store_bytes(occ, occ4, p0, n, codes);
     }
     if (!counts) return;                                                           // uniform: a kernel argument
 #pragma unroll
-    for (int k = 0; k < 3; ++k)
-        for (int off = 32; off >= 1; off >>= 1) cnt[k] += __shfl_xor(cnt[k], off, 64);
+    for (int k = 0; k < 3; ++k) cnt[k] = wave_sum(cnt[k]);
     if ((threadIdx.x & 63) == 0)
         for (int k = 0; k < 3; ++k) red[threadIdx.x >> 6][k] = cnt[k];
     __syncthreads();
@@ -114,10 +94,8 @@ extern "C" int vps_flow_occlusion(const float* fwd, int fwd_ld, int fwd_coff, co
     if (fwd_coff < 0 || fwd_ld < fwd_coff + 2 || back_coff < 0 || back_ld < back_coff + 2) return VPS_EARG(3);
     if ((uintptr_t)counts & 7) return VPS_EARG(4);
     if (!(alpha >= 0.f) || !(beta >= 0.f)) return VPS_EARG(5);                      // negative or NaN
-    const int fmode = (fwd_ld == 2 && fwd_coff == 0 && ((uintptr_t)fwd & 15) == 0) ? 2
-                    : ((fwd_ld & 1) == 0 && ((uintptr_t)(fwd + fwd_coff) & 7) == 0) ? 1 : 0;
-    const int bpair = (back_ld & 1) == 0 && ((uintptr_t)(back + back_coff) & 7) == 0;
-    const long nchunk = ((long)H * W + OCC_PIX - 1) / OCC_PIX;
+    const int fmode = px4_flow_mode(fwd, fwd_ld, fwd_coff), bpair = px4_flow_mode(back, back_ld, back_coff) >= 1;
+    const long nchunk = ((long)H * W + PX4 - 1) / PX4;
     long g = (nchunk + OCC_THREADS - 1) / OCC_THREADS; if (g > 2048) g = 2048;      // <= 8 workgroups per CU, then grid-stride
     hipLaunchKernelGGL(flow_occlusion_kernel, dim3((unsigned)g), dim3(OCC_THREADS), 0, (hipStream_t)stream, fwd, fwd_ld, fwd_coff, fmode, back, back_ld,
                        back_coff, bpair, H, W, alpha, beta, occ, reinterpret_cast<unsigned long long*>(counts));

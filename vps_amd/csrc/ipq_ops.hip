@@ -5,7 +5,7 @@
 //   vps_segment_stats_ch   vps_segment_stats with the id taken from a chosen channel: (0, 1) is the key of
 //   vps_segment_paint_ch   _converter_2ch_single_core (base_dataset.py:288-335), 1000 * pan_seg + pan_ins
 // Integer work, bit-exact against the reference functions (tests/test_ipq_gpu.py, goldens from the real functions).
-#include "common.h"
+#include "px4.h"
 
 namespace {
 
@@ -69,16 +69,12 @@ void sseg_confusion_kernel(const uint8_t* __restrict__ gt, int Hg, int Wg, const
         }
         // the run each lane is left with: one add per wavefront where all of them are the same pair
         const bool has = run_len > 0;
-        const unsigned long long act = __ballot(has);
-        if (act) {
-            const int first = __shfl(run_key, __ffsll((long long)act) - 1, 64);
-            if (__ballot(has && run_key != first) == 0) {
-                int sum = has ? run_len : 0;
-                for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
-                if (lane == 0) atomicAdd(&h[first], sum);
-            } else if (has) {
-                atomicAdd(&h[run_key], run_len);
-            }
+        int src;
+        uint32_t sum;
+        if (wave_same_run(has, (uint32_t)run_key, run_len, src, sum)) {
+            if (lane == src) atomicAdd(&h[run_key], (int)sum);
+        } else if (has) {
+            atomicAdd(&h[run_key], run_len);
         }
     }
     __syncthreads();

@@ -3,54 +3,15 @@
 //                          confusion matrix, the size of every gt track and predicted track, and their intersections. The tables stay
 //                          on the device for the whole video; nothing is zeroed, downloaded or synchronised here.
 // Integer work: the result does not depend on the order of the adds, so two runs give identical tables.
-#include "common.h"
+#include "px4.h"
 
 namespace {
 
 constexpr int STQ_THREADS = 256;
-constexpr int STQ_PIX = 4;                            // pixels per lane and step: 12 bytes = 3 dwords of each map
 constexpr int STQ_LDS_CELLS = 12288;                  // 48 KiB of uint32 cells per workgroup: 3 workgroups in the 160 KiB of a CU
 constexpr long STQ_MAX_CELLS = 1L << 26;              // all four tables together: 512 MiB of int64
 
 struct StqTables { unsigned long long *conf, *gt_size, *pred_size, *inter; };
-
-__device__ __forceinline__ int stq_id_index(const uint32_t* __restrict__ ids, int n, uint32_t v) {
-    int lo = 0, hi = n - 1;
-    while (lo <= hi) {                                // sorted, unique
-        const int mid = (lo + hi) >> 1;
-        const uint32_t m = ids[mid];
-        if (m == v) return mid;
-        if (m < v) lo = mid + 1; else hi = mid - 1;
-    }
-    return n;                                         // not listed
-}
-
-// The ids of pixels 4 * ch .. 4 * ch + n - 1 of a [npix][3] byte map whose base need not be dword-aligned. The 12 bytes sit in 3 aligned
-// dwords (4 when the base is off a dword boundary); they are loaded as dwords and shifted into place. A chunk whose dwords would reach
-// in front of the base or past byte 3 * npix (the first one of an unaligned map, the last one or two of any map) is read byte by byte.
-__device__ __forceinline__ void stq_load_ids(const uint8_t* __restrict__ p, long nbytes, long ch, int n, uint32_t (&id)[STQ_PIX]) {
-    const unsigned o = (unsigned)((uintptr_t)p & 3);
-    const long b0 = 12 * ch;                          // first byte of the chunk's dwords, counted from the aligned address p - o
-    if (b0 >= (long)o && b0 + (o ? 16 : 12) <= (long)o + nbytes) {
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(p - o) + 3 * ch;
-        const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = o ? w[3] : 0u;
-        const uint32_t d0 = __builtin_amdgcn_alignbyte(w1, w0, o), d1 = __builtin_amdgcn_alignbyte(w2, w1, o),
-                       d2 = __builtin_amdgcn_alignbyte(w3, w2, o);
-        id[0] = d0 & 0xffffffu;
-        id[1] = (d0 >> 24) | ((d1 & 0xffffu) << 8);
-        id[2] = (d1 >> 16) | ((d2 & 0xffu) << 16);
-        id[3] = d2 >> 8;
-    } else {
-#pragma unroll
-        for (int i = 0; i < STQ_PIX; ++i) {
-            id[i] = 0;
-            if (i < n) {
-                const uint8_t* a = p + b0 + 3 * i;
-                id[i] = a[0] | (a[1] << 8) | (a[2] << 16);
-            }
-        }
-    }
-}
 
 // the cells one (G, P) pair adds to; -1 = none
 struct StqCells { int conf, gt, pred, inter; };
@@ -87,18 +48,18 @@ void stq_accumulate_kernel(const uint8_t* __restrict__ gt, const uint8_t* __rest
         __syncthreads();
     }
     const int lane = threadIdx.x & 63;
-    const long nbytes = 3 * npix, nchunk = (npix + STQ_PIX - 1) / STQ_PIX;
+    const long nbytes = 3 * npix, nchunk = (npix + PX4 - 1) / PX4;
     for (long ch0 = (long)blockIdx.x * STQ_THREADS; ch0 < nchunk; ch0 += (long)gridDim.x * STQ_THREADS) {     // uniform per workgroup
         const long ch = ch0 + threadIdx.x;
         uint32_t run_g = 0xffffffffu, run_p = 0xffffffffu, run_len = 0;       // ids are below 2^24
         StqCells cell = {-1, -1, -1, -1};
         if (ch < nchunk) {
-            const int n = (int)min((long)STQ_PIX, npix - STQ_PIX * ch);
-            uint32_t G[STQ_PIX], P[STQ_PIX];
-            stq_load_ids(gt, nbytes, ch, n, G);
-            stq_load_ids(pred, nbytes, ch, n, P);
+            const int n = (int)min((long)PX4, npix - PX4 * ch);
+            uint32_t G[PX4], P[PX4];
+            px4_load_px3(gt, nbytes, ch, n, G);
+            px4_load_px3(pred, nbytes, ch, n, P);
 #pragma unroll
-            for (int i = 0; i < STQ_PIX; ++i) {
+            for (int i = 0; i < PX4; ++i) {
                 if (i >= n) break;
                 if (G[i] != run_g || P[i] != run_p) {
                     if (run_len) stq_add<LDS>(cell, run_len, stq_tab, o_gt, o_pred, o_inter, t);
@@ -106,7 +67,7 @@ void stq_accumulate_kernel(const uint8_t* __restrict__ gt, const uint8_t* __rest
                     // ---- the definition's per-pixel rules, once per run
                     int gi = -1, cg = C; bool gthing = false, crowd = false;
                     if (run_g) {
-                        gi = stq_id_index(gt_ids, ngt, run_g);
+                        gi = px4_sorted_index(gt_ids, ngt, run_g);
                         if (gi < ngt) {
                             const int info = gt_info[gi];
                             if ((info & 63) < C) { cg = info & 63; gthing = info & 64; crowd = gthing && (info & 128); }
@@ -114,7 +75,7 @@ void stq_accumulate_kernel(const uint8_t* __restrict__ gt, const uint8_t* __rest
                     }
                     int pi = -1, cp = C; bool pthing = false, unlisted = false;
                     if (run_p) {
-                        pi = stq_id_index(pred_ids, npred, run_p);
+                        pi = px4_sorted_index(pred_ids, npred, run_p);
                         if (pi < npred) {
                             const int info = pred_info[pi];
                             if ((info & 63) < C) { cp = info & 63; pthing = info & 64; }
@@ -133,17 +94,12 @@ void stq_accumulate_kernel(const uint8_t* __restrict__ gt, const uint8_t* __rest
         }
         // the run each lane is left with: one add per wavefront where all of them are the same pair
         const bool has = run_len > 0;
-        const unsigned long long act = __ballot(has);
-        if (act) {
-            const int src = __ffsll((long long)act) - 1;
-            const uint32_t fg = __shfl(run_g, src, 64), fp = __shfl(run_p, src, 64);
-            if (__ballot(has && (run_g != fg || run_p != fp)) == 0) {
-                uint32_t sum = has ? run_len : 0;
-                for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
-                if (lane == src) stq_add<LDS>(cell, sum, stq_tab, o_gt, o_pred, o_inter, t);
-            } else if (has) {
-                stq_add<LDS>(cell, run_len, stq_tab, o_gt, o_pred, o_inter, t);
-            }
+        int src;
+        uint32_t sum;
+        if (wave_same_run(has, run_g | (uint64_t)run_p << 32, run_len, src, sum)) {
+            if (lane == src) stq_add<LDS>(cell, sum, stq_tab, o_gt, o_pred, o_inter, t);
+        } else if (has) {
+            stq_add<LDS>(cell, run_len, stq_tab, o_gt, o_pred, o_inter, t);
         }
     }
     if (LDS) {
@@ -174,7 +130,7 @@ extern "C" int vps_stq_accumulate(const uint8_t* gt_rgb, const uint8_t* pred_rgb
     if (((uintptr_t)conf | (uintptr_t)gt_size | (uintptr_t)pred_size | (uintptr_t)inter) & 7) return VPS_EARG(6);
     StqTables t = {reinterpret_cast<unsigned long long*>(conf), reinterpret_cast<unsigned long long*>(gt_size),
                    reinterpret_cast<unsigned long long*>(pred_size), reinterpret_cast<unsigned long long*>(inter)};
-    const long nchunk = (npix + STQ_PIX - 1) / STQ_PIX;
+    const long nchunk = (npix + PX4 - 1) / PX4;
     long g = nchunk / (STQ_THREADS * 4); if (g > 512) g = 512; if (g < 1) g = 1;          // >= 4 chunks per lane, <= 2 workgroups per CU
     hipStream_t s = (hipStream_t)stream;
     if (cells <= STQ_LDS_CELLS)                                                             // the path depends on the table sizes alone

@@ -6,54 +6,15 @@
 //   vps_tc_accumulate_masked   the same with a byte mask (vps_flow_occlusion's): an in-view pixel whose mask byte is not 0 is counted in
 //                          one extra cell and in nothing else
 // Integer adds only: the result does not depend on their order, so two runs (and the two table paths) give identical tables.
-#include "common.h"
+#include "px4.h"
 #include <string.h>
 
 namespace {
 
 constexpr int TC_THREADS = 256;
-constexpr int TC_PIX = 4;                             // pixels of cur per lane and step: 12 bytes = 3 dwords of the map, 4 bytes of the output
 
 struct TcClasses { uint32_t w[64]; };                 // seg_class[256], handed over in the kernel arguments
 struct TcTables { unsigned long long *conf, *prev_size, *cur_size, *same, *misc, *masked; };   // masked: the MASKED instances only
-
-__device__ __forceinline__ int tc_key_index(const uint16_t* __restrict__ keys, int n, uint32_t v) {
-    int lo = 0, hi = n - 1;
-    while (lo <= hi) {                                // sorted, unique
-        const int mid = (lo + hi) >> 1;
-        const uint32_t m = keys[mid];
-        if (m == v) return mid;
-        if (m < v) lo = mid + 1; else hi = mid - 1;
-    }
-    return n;                                         // not listed
-}
-
-// The three bytes (as one 24-bit value, channel 0 lowest) of pixels 4 * ch .. 4 * ch + n - 1 of a [npix][3] byte map whose base need not
-// be dword-aligned: the 12 bytes sit in 3 aligned dwords (4 when the base is off a dword boundary), loaded as dwords and shifted into
-// place. A chunk whose dwords would reach in front of the base or past byte 3 * npix is read byte by byte (stq_ops.hip has the same).
-__device__ __forceinline__ void tc_load_px(const uint8_t* __restrict__ p, long nbytes, long ch, int n, uint32_t (&px)[TC_PIX]) {
-    const unsigned o = (unsigned)((uintptr_t)p & 3);
-    const long b0 = 12 * ch;                          // first byte of the chunk's dwords, counted from the aligned address p - o
-    if (b0 >= (long)o && b0 + (o ? 16 : 12) <= (long)o + nbytes) {
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(p - o) + 3 * ch;
-        const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = o ? w[3] : 0u;
-        const uint32_t d0 = __builtin_amdgcn_alignbyte(w1, w0, o), d1 = __builtin_amdgcn_alignbyte(w2, w1, o),
-                       d2 = __builtin_amdgcn_alignbyte(w3, w2, o);
-        px[0] = d0 & 0xffffffu;
-        px[1] = (d0 >> 24) | ((d1 & 0xffffu) << 8);
-        px[2] = (d1 >> 16) | ((d2 & 0xffu) << 16);
-        px[3] = d2 >> 8;
-    } else {
-#pragma unroll
-        for (int i = 0; i < TC_PIX; ++i) {
-            px[i] = 0;
-            if (i < n) {
-                const uint8_t* a = p + b0 + 3 * i;
-                px[i] = a[0] | (a[1] << 8) | (a[2] << 16);
-            }
-        }
-    }
-}
 
 // the cells one run of in-view (warped, cur) pairs adds to; -1 = none
 struct TcCells { int conf, prev, cur, same; };
@@ -98,11 +59,10 @@ void tc_accumulate_kernel(const uint8_t* __restrict__ prev, const uint8_t* __res
         for (int i = threadIdx.x; i < cells; i += TC_THREADS) tab[i] = 0;
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    const long npix = (long)H * W, nbytes = 3 * npix, nchunk = (npix + TC_PIX - 1) / TC_PIX;
+    const long npix = (long)H * W, nbytes = 3 * npix, nchunk = (npix + PX4 - 1) / PX4;
     const float xmax = (float)(W - 1), ymax = (float)(H - 1);
     const int sh = 8 * idch;
     const bool flick4 = flick && ((uintptr_t)flick & 3) == 0;
-    const bool mask4 = MASKED && ((uintptr_t)mask & 3) == 0;
     uint32_t n_in = 0, n_out = 0, n_msk = 0;
     for (long ch0 = (long)blockIdx.x * TC_THREADS; ch0 < nchunk; ch0 += (long)gridDim.x * TC_THREADS) {       // uniform per workgroup
         const long ch = ch0 + threadIdx.x;
@@ -110,37 +70,17 @@ void tc_accumulate_kernel(const uint8_t* __restrict__ prev, const uint8_t* __res
         bool run_in = false, run_msk = false;
         TcCells cell = {-1, -1, -1, -1};
         if (ch < nchunk) {
-            const long p0 = TC_PIX * ch;
-            const int n = (int)min((long)TC_PIX, npix - p0);
-            uint32_t A[TC_PIX];
-            tc_load_px(cur, nbytes, ch, n, A);
-            float u[TC_PIX], v[TC_PIX];
-            if (fmode == 2 && n == TC_PIX) {
-                const float4 f0 = *reinterpret_cast<const float4*>(flow + 2 * p0), f1 = *reinterpret_cast<const float4*>(flow + 2 * p0 + 4);
-                u[0] = f0.x; v[0] = f0.y; u[1] = f0.z; v[1] = f0.w; u[2] = f1.x; v[2] = f1.y; u[3] = f1.z; v[3] = f1.w;
-            } else {
-#pragma unroll
-                for (int i = 0; i < TC_PIX; ++i) {
-                    u[i] = v[i] = 0.f;
-                    if (i < n) {
-                        const float* f = flow + (p0 + i) * ld + coff;
-                        if (fmode >= 1) { const float2 g = *reinterpret_cast<const float2*>(f); u[i] = g.x; v[i] = g.y; }
-                        else { u[i] = f[0]; v[i] = f[1]; }
-                    }
-                }
-            }
-            uint32_t M = 0;                           // the chunk's mask bytes
-            if (MASKED) {
-                if (mask4 && n == TC_PIX) {
-                    M = *reinterpret_cast<const uint32_t*>(mask + p0);
-                } else {
-                    for (int i = 0; i < n; ++i) M |= (uint32_t)mask[p0 + i] << (8 * i);
-                }
-            }
+            const long p0 = PX4 * ch;
+            const int n = (int)min((long)PX4, npix - p0);
+            uint32_t A[PX4];
+            px4_load_px3(cur, nbytes, ch, n, A);
+            float u[PX4], v[PX4];
+            px4_load_flow(flow, ld, coff, fmode, p0, n, u, v);
+            const uint32_t M = MASKED ? px4_load_bytes(mask, npix, p0, n) : 0;      // the chunk's mask bytes
             int y = (int)(p0 / W), x = (int)(p0 - (long)y * W);
             uint32_t codes = 0;
 #pragma unroll
-            for (int i = 0; i < TC_PIX; ++i) {
+            for (int i = 0; i < PX4; ++i) {
                 if (i >= n) break;
                 // ---- the definition's warp: fp32, one add each, compared as floats before any conversion
                 const float sx = (float)x + u[i], sy = (float)y + v[i];
@@ -173,7 +113,7 @@ void tc_accumulate_kernel(const uint8_t* __restrict__ prev, const uint8_t* __res
                         int ca = cls[ak >> 8], cb = cls[bk >> 8];
                         if (ca > C) ca = C;
                         if (cb > C) cb = C;
-                        const int ka = tc_key_index(keys, nkeys, ak), kb = ak == bk ? ka : tc_key_index(keys, nkeys, bk);
+                        const int ka = px4_sorted_index(keys, nkeys, ak), kb = ak == bk ? ka : px4_sorted_index(keys, nkeys, bk);
                         cell.conf = cb * C1 + ca;
                         cell.cur = ka < nkeys ? ka : -1;
                         cell.prev = kb < nkeys ? kb : -1;
@@ -185,34 +125,21 @@ void tc_accumulate_kernel(const uint8_t* __restrict__ prev, const uint8_t* __res
                 codes |= code << (8 * i);
                 if (++x == W) { x = 0; ++y; }
             }
-            if (flick) {
-                if (flick4 && n == TC_PIX) {
-                    *reinterpret_cast<uint32_t*>(flick + p0) = codes;
-                } else {
-                    for (int i = 0; i < n; ++i) flick[p0 + i] = (uint8_t)(codes >> (8 * i));
-                }
-            }
+            if (flick) px4_store_bytes(flick, flick4, p0, n, codes);
         }
         // the in-view run each lane is left with: one add per wavefront where all of them are the same
         const bool has = run_len > 0;
-        const unsigned long long act = __ballot(has);
-        if (act) {
-            const int src = __ffsll((long long)act) - 1;
-            const uint32_t fs = __shfl(run_st, src, 64);
-            if (__ballot(has && (!run_in || run_st != fs)) == 0) {
-                uint32_t sum = has ? run_len : 0;
-                for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
-                if (lane == src) tc_add<LDS>(cell, sum, tab, o_prev, o_cur, o_same, t);
-            } else if (has && run_in) {
-                tc_add<LDS>(cell, run_len, tab, o_prev, o_cur, o_same, t);
-            }
+        int src;
+        uint32_t sum;
+        if (wave_same_run(has, run_st | (uint64_t)run_in << 32 | (uint64_t)run_msk << 33, run_len, src, sum)) {
+            if (lane == src && run_in) tc_add<LDS>(cell, sum, tab, o_prev, o_cur, o_same, t);
+        } else if (has && run_in) {
+            tc_add<LDS>(cell, run_len, tab, o_prev, o_cur, o_same, t);
         }
     }
-    for (int off = 32; off >= 1; off >>= 1) {
-        n_in += __shfl_xor(n_in, off, 64);
-        n_out += __shfl_xor(n_out, off, 64);
-        if (MASKED) n_msk += __shfl_xor(n_msk, off, 64);
-    }
+    n_in = wave_sum(n_in);
+    n_out = wave_sum(n_out);
+    if (MASKED) n_msk = wave_sum(n_msk);
     if (lane == 0) {
         if (LDS) {
             if (n_in) atomicAdd(&tab[o_misc], n_in);
@@ -255,10 +182,9 @@ static int tc_launch(const uint8_t* prev, const uint8_t* cur, int H, int W, cons
                   reinterpret_cast<unsigned long long*>(misc), reinterpret_cast<unsigned long long*>(masked)};
     TcClasses sc;
     memcpy(sc.w, seg_class, 256);                                                // the caller's table may go once the call returns
-    const int fmode = (flow_ld == 2 && flow_coff == 0 && ((uintptr_t)flow & 15) == 0) ? 2
-                    : ((flow_ld & 1) == 0 && ((uintptr_t)(flow + flow_coff) & 7) == 0) ? 1 : 0;
+    const int fmode = px4_flow_mode(flow, flow_ld, flow_coff);
     const long cells = (long)(num_classes + 1) * (num_classes + 1) + 3L * nkeys + (mask ? 3 : 2);
-    const long nchunk = ((long)H * W + TC_PIX - 1) / TC_PIX;
+    const long nchunk = ((long)H * W + PX4 - 1) / PX4;
     long g = nchunk / (TC_THREADS * 4); if (g > 512) g = 512; if (g < 1) g = 1;            // >= 4 chunks per lane, <= 2 workgroups per CU
     hipStream_t s = (hipStream_t)stream;
     const bool lds = cells <= vps_stq_lds_cells();                                          // the path depends on the table sizes alone
