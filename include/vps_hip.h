@@ -761,6 +761,52 @@ int vps_flow_error(const float* pred, int pred_ld, int pred_coff, const float* g
                    const uint8_t* occ_pred, int H, int W, int64_t* counts, double* sums, uint8_t* err_rgb, void* ws, int64_t ws_bytes,
                    void* stream);
 
+/* Flow quality without ground truth (csrc/flow_photo_ops.hip, vps_amd/flowphoto.py): the photometric warp error of ONE
+ * (cur, prev, flow) triple - prev sampled at p + flow(p) against cur - beside the static error of prev(p) against cur(p). It is the warp /
+ * interpolation error that Middlebury reports beside EPE, restated from memory (vps_amd/flowphoto.py). Two launches on `stream` (the
+ * counting pass, then one workgroup that adds the partial sums); the call does not synchronise, allocate or zero.
+ *   cur_bgr, prev_bgr  DEVICE uint8 [H][W][3] frames, any byte alignment; nothing outside their 3 H W bytes is read
+ *   flow         DEVICE fp32 NHWC map on the grid of cur, pointing into prev, pixel p at flow[p * flow_ld + flow_coff] (x) and [.. + 1] (y)
+ *                as vps_tc_accumulate's; any 4-byte aligned base. Read as 16-byte loads when it is the dense [h,w,2] copy on a 16-byte
+ *                boundary, as 8-byte loads when flow_ld is even and flow + flow_coff is 8-byte aligned, as 4-byte loads otherwise
+ *   mask_in      NULL, or DEVICE uint8 [H][W], any byte alignment, vps_flow_occlusion's codes: 0 puts a pixel into group 0, any other
+ *                byte into group 1. NULL: every pixel is in group 0
+ *   thr          the flag threshold in grey levels; negative or NaN is refused
+ *   counts       DEVICE int64 [21], 8-byte aligned, ADDED to: [g * 10 + k] for the groups g = 0, 1 and cell 20 = pixels not in view.
+ *                k: 0 n, 1 flagged, 2 sum of as, 3 sum of qs, 4 / 5 / 6 / 7 pixels with e > 4 / 8 / 16 / 32, 8 pixels with
+ *                aw < double(as) (the flow helps), 9 pixels with aw > double(as). Cells 0 of both groups and cell 20 together grow by
+ *                H W per call
+ *   sums         DEVICE double [2][2], 8-byte aligned, ADDED to: per group the sum of aw and the sum of qw
+ *   mask_out     NULL, or DEVICE uint8 [H][W], any byte alignment, every byte written. It MAY BE THE SAME BUFFER as mask_in: a lane reads
+ *                its own four bytes before it writes them
+ *   residual     NULL, or DEVICE uint8 [H][W], any byte alignment, every byte written
+ *   ws           DEVICE workspace, 8-byte aligned, at least vps_flow_photo_ws_bytes(H, W) bytes (HOST arithmetic; -1002 for a bad size):
+ *                four doubles per workgroup of the counting launch
+ * Per pixel p = (x, y) of cur, in this order, every operation rounded on its own (no contraction):
+ *   1. in view, fp32: u, v = flow(p); sx = float(x) + u, sy = float(y) + v; in view iff floorf(sx + 0.5f) and floorf(sy + 0.5f) lie in
+ *      [0, W-1] and [0, H-1], compared as floats (vps_tc_accumulate's rule: NaN, +-inf, 1e30 fall out; no index is formed from a float
+ *      before this test has passed). Not in view: counts[20] += 1, mask_out = 2, residual = 0, nothing else
+ *   2. group: g = 0 when mask_in is NULL or mask_in[p] == 0, otherwise 1
+ *   3. bilinear sample, fp32, corners and weights as vps_flow_occlusion forms them: x0 = floorf(sx), wx = sx - x0, x1 = x0 + 1, both
+ *      clamped to [0, W-1] after conversion to int; the same for y. Per channel c, the corner bytes of prev converted to float:
+ *      top = b00 + wx*(b01 - b00), bot = b10 + wx*(b11 - b10), s_c = top + wy*(bot - top)
+ *   4. errors, fp64: dw_c = double(s_c) - double(cur_c); aw = (|dw_0| + |dw_1|) + |dw_2|; qw = (dw_0*dw_0 + dw_1*dw_1) + dw_2*dw_2;
+ *      e = aw / 3.0. The static twin from prev(p) itself, exact integers: as = sum |prev_c(p) - cur_c(p)|, qs = sum (prev_c(p) - cur_c(p))^2
+ *   5. flagged iff e > double(thr), strictly
+ *   6. the cells of counts[g * 10 + k] above; sums[g][0] += aw, sums[g][1] += qw
+ *   7. mask_out[p] = mask_in[p] when that is non-zero, else 3 when flagged, else 0
+ *   8. residual[p] = min(255, (int)floor(e + 0.5))
+ * Determinism: as vps_flow_error - one 64-bit integer atomic per non-zero cell and workgroup; the sums are reduced in a fixed tree inside
+ * the workgroup, written to the workgroup's own slot of ws, and the second launch adds the slots in a fixed order before it adds the
+ * totals to `sums`: no floating-point atomics, the same bytes on every call, twice without zeroing is exactly double. Every corner
+ * address of prev is clamped to the map. Errors before any launch: -1001 cur_bgr, prev_bgr, flow, counts, sums or ws NULL; -1002 H or
+ * W < 1 or H W >= 2^31; -1003 flow_coff < 0 or flow_ld < flow_coff + 2; -1004 counts or sums not 8-byte aligned, or the flow base not
+ * 4-byte aligned; -1005 ws not 8-byte aligned or ws_bytes too small; -1006 thr negative or NaN. */
+int64_t vps_flow_photo_ws_bytes(int H, int W);
+int vps_flow_photo(const uint8_t* cur_bgr, const uint8_t* prev_bgr, int H, int W, const float* flow, int flow_ld, int flow_coff,
+                   const uint8_t* mask_in, float thr, int64_t* counts, double* sums, uint8_t* mask_out, uint8_t* residual, void* ws,
+                   int64_t ws_bytes, void* stream);
+
 /* Boundary PQ / boundary VPQ (csrc/boundary_ops.hip, vps_amd/boundary.py): the boundary band of EVERY segment of a
  * panoptic map in one call, the device form of Boundary IoU's mask_to_boundary (Cheng et al., CVPR 2021) applied per segment.
  *   pan_rgb   DEVICE uint8 [H][W][3] panoptic map (segment id = R + 256 G + 65536 B, the maps vps_pair_count reads); any byte alignment,

@@ -84,6 +84,15 @@ def parse_args(argv=None):
                     'counted); pixels where the two flows do not cancel (disocclusions) are left out of the counts and reported as the occluded share '
                     '(OCC in tc.txt, grey in the --tc-map images; off by default)')
     ap.add_argument('--dry-run', action='store_true')
+    ap.add_argument('--flow-photo', action='store_true', help='flow quality without ground truth (vps_amd.flowphoto), also with --video: the photometric warp '
+                    'error of every frame\'s flow between the frame and the previous one of its video, beside the static error of not warping; '
+                    'flow-photo.txt and flow-photo.json beside pred.json (keeps the flow and the decoded frame of every frame; with --tc-occlusion the '
+                    'occlusion mask splits the pixels into a visible and a masked group; flagged above --tc-photometric if given, else 16 grey levels; '
+                    'off by default)')
+    ap.add_argument('--flow-photo-map', default=None, metavar='DIR', help='--flow-photo: write DIR/<name>.jpg for every frame but a video\'s first, the '
+                    'photometric residual blended over the frame')
+    ap.add_argument('--tc-photometric', type=float, default=None, metavar='THR', help='--tc-occlusion, and pixels that are in view and not occluded but whose '
+                    'photometric warp error is above THR grey levels are left out of the counts too (they are part of OCC then; off by default)')
     ap.add_argument('--dry-size', default='128x256'); ap.add_argument('--dry-videos', type=int, default=1); ap.add_argument('--dry-frames', type=int, default=16)
     ap.add_argument('--check-only', action='store_true')
     return ap.parse_args(argv)
@@ -215,7 +224,10 @@ def run(args, tmp):
     model.ensure_packed(dev)
     prep = DeviceImagePrep(**cfg.img_norm_cfg, size_divisor=32, img_scale=(2048, 1024), device=dev)
     files = [os.path.join(img_prefix, x['file_name']) for x in info]
-    keep = bool(args.overlay or args.overlay_video or args.tc_map)
+    if args.tc_photometric is not None:
+        args.tc_occlusion = True
+    with_photo = bool(args.flow_photo or args.flow_photo_map)
+    keep = bool(args.overlay or args.overlay_video or args.tc_map or with_photo or args.tc_photometric is not None)
     with_tc = bool(args.tc or args.tc_map or args.tc_occlusion)
     if reader is not None:
         assert len(reader) > 0, '%s holds no complete frame' % args.video
@@ -228,7 +240,7 @@ def run(args, tmp):
         from vps_amd.flowvis import FlowWriter, flow_name
         model.keep_flow = True
         flow_writer = FlowWriter(dev, fmt=args.flow_format, max_rad=args.flow_max_rad, entropy=args.jpeg_entropy)
-    if with_tc:
+    if with_tc or with_photo:
         model.keep_flow = True
         res['all_flows'] = []
     if args.tc_occlusion:
@@ -253,7 +265,7 @@ def run(args, tmp):
                 res['all_frames'].append(feeder.frame(idx))       # the decoded BGR frame the feeder holds anyway
             if flow_writer is not None:
                 flow_writer.submit(result[2]['flow'], flow_name(args.flow, files[idx], args.flow_format))
-            if with_tc:
+            if with_tc or with_photo:
                 res['all_flows'].append(result[2]['flow'])
             if args.tc_occlusion:                            # the flow from the previous frame to this one: a second FlowNet2 pass, behind the frame
                 res['all_back_flows'].append(model.flow_between(ref, img, img_shape=meta['img_shape']) if idx % span > 0 else None)
@@ -293,13 +305,30 @@ def run(args, tmp):
         tb = kw['tubes'].result()
         report['tubes'] = dict(file=os.path.join(output_dir, 'tubes.json'), videos=len(tb['videos']), tracks=sum(len(v['tracks']) for v in tb['videos']))
         kw['tubes'].close()
+    if with_photo:                                          # a key of its own: without the options the report is what it was
+        from run_vps_synthetic import photo_report
+        from vps_amd import flowphoto
+        order = sorted(range(len(res['all_names'])), key=lambda i: res['all_names'][i])                # the order of pred_pans_2ch
+        pev = flowphoto.PhotoEvaluator(dev, thr=flowphoto.PHOTO_THR if args.tc_photometric is None else args.tc_photometric, per_pair=True)
+        pfiles = flowphoto.score_videos(pev, [res['all_frames'][i] for i in order], [res['all_flows'][i] for i in order], [res['all_names'][i] for i in order],
+                                        span, back_flows=[res['all_back_flows'][i] for i in order] if args.tc_occlusion else None,
+                                        map_dir=args.flow_photo_map, alpha=args.overlay_alpha, quality=args.overlay_quality, entropy=args.jpeg_entropy)
+        pr = pev.result()
+        flowphoto.write_outputs(pr, output_dir)
+        pr['map_files'] = pfiles
+        report['flow_photo'] = dict(photo_report(pr), file=os.path.join(output_dir, 'flow-photo.txt'))
+        print('flow photo  MAE warped %.4f  static %.4f  ratio %.4f' % tuple(report['flow_photo'][k] for k in ('mae_warp', 'mae_static', 'ratio')))
     if with_tc:                                             # a key of its own: without the options the report is what it was
         from vps_amd import tc
         nseg = 19                                           # PanopticUnifier(dev, 19, 9): the 19 classes are their own indices, the rest is void
         seg_class = np.full(256, 255, dtype=np.uint8)
         seg_class[:nseg] = np.arange(nseg)
         okw = {}
-        if args.tc_occlusion:
+        if args.tc_photometric is not None:
+            ev = tc.TcEvaluator(seg_class, nseg, id_channel=2, device=dev, per_pair=True, id_last_stuff=unifier.id_last_stuff, occlusion=True,
+                                photometric=args.tc_photometric)
+            report['tc_photometric'] = dict(thr=args.tc_photometric)
+        elif args.tc_occlusion:
             ev = tc.TcEvaluator(seg_class, nseg, id_channel=2, device=dev, per_pair=True, id_last_stuff=unifier.id_last_stuff, occlusion=True)
         else:
             ev = tc.TcEvaluator(seg_class, nseg, id_channel=2, device=dev, per_pair=True, id_last_stuff=unifier.id_last_stuff)
@@ -310,7 +339,8 @@ def run(args, tmp):
             okw['back_flows'] = [res['all_back_flows'][i] for i in order]
             res['all_back_flows'] = None
         tfiles = tc.score_videos(ev, pred_pans_2ch, flows, [res['all_names'][i] for i in order], span, map_dir=args.tc_map,
-                                 frames=[res['all_frames'][i] for i in order] if args.tc_map else None, alpha=args.overlay_alpha,
+                                 frames=[res['all_frames'][i] for i in order] if (args.tc_map or args.tc_photometric is not None) else None,
+                                 alpha=args.overlay_alpha,
                                  quality=args.overlay_quality, entropy=args.jpeg_entropy, **okw)
         r = ev.result()
         tc.write_outputs(r, output_dir)

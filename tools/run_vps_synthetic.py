@@ -117,7 +117,7 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg
 
 
 def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_png=False, overlay=None, tubes=False, jpeg_entropy='host',
-                overlay_video=None, tc=None):
+                overlay_video=None, tc=None, flow_photo=None):
     """test_vpq.py:178-198 with the device-side unifier / converter / asynchronous writer (`device_png`: the PNGs are filtered and
     deflated on the device too, postprocess.DevicePngWriter). `overlay` = (directory, quality, alpha): an overlay JPEG of EVERY frame,
     blended and transformed on the device (postprocess.write_overlays). `tubes`: tubes.json beside pred.json, the COCO run-length
@@ -125,13 +125,18 @@ def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_pn
     the same overlays as one Y4M stream per video (y4m.Y4mWriter), beside the JPEGs or, without `overlay`, instead of them; its
     'files' entry receives the streams' names. `tc` = dict(map_dir, alpha, quality): the temporal consistency of EVERY video's consecutive
     frames from res['all_flows'] (vps_amd.tc; tc.txt and tc-tracks.json beside pred.json, the inconsistency overlays in map_dir if it
-    is given; with 'occlusion' the forward-backward check on res['all_back_flows'] first); its 'result' entry receives the figures"""
+    is given; with 'occlusion' the forward-backward check on res['all_back_flows'] first; with 'photometric' = THR the photometric flag of
+    vps_amd.flowphoto on top of it); its 'result' entry receives the figures. `flow_photo` = dict(map_dir, thr, alpha, quality): the
+    photometric warp error of the run's own flows between the decoded frames (vps_amd.flowphoto; flow-photo.txt and flow-photo.json
+    beside pred.json, the residual overlays in map_dir if it is given), before `tc` lets the flows go; its 'result' entry likewise"""
     from vps_amd.postprocess import DevicePngWriter, PanopticUnifier, inference_panoptic_video, write_overlays
     unifier = PanopticUnifier(dev, 19, 9)
     two = unifier.get_unified_pan_result(res['all_ssegs'], res['all_panos'], res['all_pano_cls_inds'], obj_ids=res['all_pano_obj_ids'],
                                          stuff_area_limit=2048, names=res['all_names'])
     keys = sorted(two.keys())
     pred_pans_2ch = [two[k] for k in keys]
+    if flow_photo is not None:
+        flow_photo['result'] = photo_score(pred_pans_2ch, res, keys, len(keys) // max(videos, 1), dev, out_dir, flow_photo, jpeg_entropy)
     if tc is not None:
         tc['result'] = tc_score(pred_pans_2ch, res, keys, len(keys) // max(videos, 1), dev, out_dir, unifier.id_last_stuff, tc, jpeg_entropy)
     names = keys[(labeled_fid // lambda_)::lambda_]                               # names of the labelled frames (im_jsons['images'])
@@ -159,6 +164,29 @@ def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_pn
     return names, pans, pj
 
 
+def padded_frames(res, names, maps):
+    """the decoded frames in the order of `names`, each padded with its edge pixels to the size of its map (synth_frame crops the late,
+    far-shifted frames of a clip at the edge of its noise field while img_meta keeps the nominal size)"""
+    at = {n: i for i, n in enumerate(res['all_names'])}
+    return [np.pad(res['all_frames'][at[n]], ((0, m.shape[0] - res['all_frames'][at[n]].shape[0]), (0, m.shape[1] - res['all_frames'][at[n]].shape[1]),
+                                               (0, 0)), mode='edge') for n, m in zip(names, maps)]
+
+
+def photo_score(maps, res, names, nframes_per_video, dev, out_dir, opt, jpeg_entropy='host'):
+    """--flow-photo: the photometric warp error of every frame's flow between the frame and its predecessor (vps_amd.flowphoto); with the
+    backward flows of --tc-occlusion the occlusion mask splits the pixels into a visible and a masked group. The flows stay where they are"""
+    from vps_amd import flowphoto
+    at = {n: i for i, n in enumerate(res['all_names'])}
+    ev = flowphoto.PhotoEvaluator(dev, thr=opt['thr'], per_pair=True)
+    back = [res['all_back_flows'][at[n]] for n in names] if res.get('all_back_flows') is not None else None
+    files = flowphoto.score_videos(ev, padded_frames(res, names, maps), [res['all_flows'][at[n]] for n in names], names, nframes_per_video, back_flows=back,
+                                   map_dir=opt.get('map_dir'), alpha=opt.get('alpha', 128), quality=opt.get('quality', 90), entropy=jpeg_entropy)
+    result = ev.result()
+    flowphoto.write_outputs(result, out_dir)
+    result['map_files'] = files
+    return result
+
+
 def tc_score(maps, res, names, nframes_per_video, dev, out_dir, id_last_stuff, opt, jpeg_entropy='host'):
     """--tc: the unified maps of every frame (in the order of `names`) against their predecessors warped by the run's own flows. The 19
     classes of CATEGORIES are the class indices, every other pan_seg value is void; tracks are keyed by pan_obj (channel 2)"""
@@ -166,7 +194,10 @@ def tc_score(maps, res, names, nframes_per_video, dev, out_dir, id_last_stuff, o
     seg_class = np.full(256, 255, dtype=np.uint8)
     seg_class[:len(CATEGORIES)] = np.arange(len(CATEGORIES))
     kw = {}
-    if opt.get('occlusion'):                              # --tc-occlusion: occluded pixels are left out of the counts
+    if opt.get('photometric') is not None:                # --tc-photometric: occluded and photometrically wrong pixels are left out of the counts
+        ev = tc.TcEvaluator(seg_class, len(CATEGORIES), id_channel=2, device=dev, per_pair=True, id_last_stuff=id_last_stuff, occlusion=True,
+                            photometric=opt['photometric'])
+    elif opt.get('occlusion'):                            # --tc-occlusion: occluded pixels are left out of the counts
         ev = tc.TcEvaluator(seg_class, len(CATEGORIES), id_channel=2, device=dev, per_pair=True, id_last_stuff=id_last_stuff, occlusion=True)
     else:
         ev = tc.TcEvaluator(seg_class, len(CATEGORIES), id_channel=2, device=dev, per_pair=True, id_last_stuff=id_last_stuff)
@@ -177,15 +208,25 @@ def tc_score(maps, res, names, nframes_per_video, dev, out_dir, id_last_stuff, o
         kw['back_flows'] = [res['all_back_flows'][at[n]] for n in names]
         res['all_back_flows'] = None
     frames = None
-    if opt.get('map_dir'):
-        frames = [np.pad(res['all_frames'][at[n]], ((0, m.shape[0] - res['all_frames'][at[n]].shape[0]), (0, m.shape[1] - res['all_frames'][at[n]].shape[1]),
-                                                     (0, 0)), mode='edge') for n, m in zip(names, maps)]
+    if opt.get('map_dir') or opt.get('photometric') is not None:
+        frames = padded_frames(res, names, maps)
     files = tc.score_videos(ev, maps, flows, names, nframes_per_video, map_dir=opt.get('map_dir'), frames=frames, alpha=opt.get('alpha', 128),
                             quality=opt.get('quality', 90), entropy=jpeg_entropy, **kw)
     result = ev.result()
     tc.write_outputs(result, out_dir)
     result['map_files'] = files
     return result
+
+
+def photo_report(r):
+    """the 'flow_photo' entry of the report from the result of vps_amd.flowphoto"""
+    a = r['all']
+    out = dict(thr=r['thr'], pairs=r['pairs'], mae_warp=round(a['mae_warp'], 6), mae_static=round(a['mae_static'], 6), ratio=round(a['ratio'], 6),
+               psnr_warp=round(a['psnr_warp'], 4), psnr_static=round(a['psnr_static'], 4), gain_db=round(a['gain_db'], 4),
+               flagged_share=round(a['flagged_share'], 6), outside_share=round(r['outside_share'], 6), map_files=len(r['map_files']))
+    if r['masked']['n']:
+        out.update(mae_warp_visible=round(r['visible']['mae_warp'], 6), mae_warp_masked=round(r['masked']['mae_warp'], 6))
+    return out
 
 
 def vpq(gt, pred, videos, nper, dev):
@@ -270,6 +311,14 @@ def parse_args(argv=None):
     ap.add_argument('--tc-occlusion', action='store_true', help='--tc with a forward-backward flow check: a second FlowNet2 pass per frame gives the flow from '
                     'the previous frame to this one, pixels where the two flows do not cancel (disocclusions) are left out of the counts and reported '
                     'as the occluded share (OCC in pred/tc.txt; grey in the --tc-map images; off by default)')
+    ap.add_argument('--flow-photo', action='store_true', help='flow quality without ground truth (vps_amd.flowphoto): the photometric warp error of every '
+                    'frame\'s flow between the frame and the previous one, beside the static error of not warping; pred/flow-photo.txt and '
+                    'pred/flow-photo.json (keeps the flow of every frame on the device; with --tc-occlusion the occlusion mask splits the pixels into a '
+                    'visible and a masked group; flagged above --tc-photometric if given, else %g grey levels; off by default)' % 16.0)
+    ap.add_argument('--flow-photo-map', default=None, metavar='DIR', help='--flow-photo: write DIR/<name>.jpg for every frame but a video\'s first, the '
+                    'photometric residual blended over the frame')
+    ap.add_argument('--tc-photometric', type=float, default=None, metavar='THR', help='--tc-occlusion, and pixels that are in view and not occluded but whose '
+                    'photometric warp error is above THR grey levels are left out of the counts too (they are part of OCC then; off by default)')
     return ap.parse_args(argv)
 
 
@@ -281,14 +330,23 @@ def main(argv=None):
     overlay_video = dict(file=args.overlay_video, sampling=args.overlay_video_sampling, files=[], alpha=args.overlay_alpha) if args.overlay_video else None
     nper = len(range(labeled_fid // lambda_, args.frames, lambda_))
     flow = (args.flow, args.flow_format, args.flow_max_rad) if args.flow else None
+    if args.tc_photometric is not None:
+        args.tc_occlusion = True
     tc = dict(map_dir=args.tc_map, alpha=args.overlay_alpha, quality=args.overlay_quality) if (args.tc or args.tc_map or args.tc_occlusion) else None
     if tc and args.tc_occlusion:
         tc['occlusion'] = True
-    res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated, flow, args.jpeg_entropy, keep_flows=tc is not None,
-                        back_flows=args.tc_occlusion)
+    if tc and args.tc_photometric is not None:
+        tc['photometric'] = args.tc_photometric
+    flow_photo = None
+    if args.flow_photo or args.flow_photo_map:
+        from vps_amd.flowphoto import PHOTO_THR
+        flow_photo = dict(map_dir=args.flow_photo_map, thr=PHOTO_THR if args.tc_photometric is None else args.tc_photometric, alpha=args.overlay_alpha,
+                          quality=args.overlay_quality)
+    res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated, flow, args.jpeg_entropy,
+                        keep_flows=tc is not None or flow_photo is not None, back_flows=args.tc_occlusion)
     t0 = time.perf_counter()
     names, pans, pj = postprocess(res, os.path.join(args.out, 'pred'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png, overlay, args.tubes,
-                                  args.jpeg_entropy, overlay_video, tc)
+                                  args.jpeg_entropy, overlay_video, tc, flow_photo)
     dpost = time.perf_counter() - t0
     pred = (pans, pj)
     gt = pred
@@ -324,6 +382,11 @@ def main(argv=None):
         if 'occluded_share' in r:
             report['tc']['occluded_share'] = round(r['occluded_share'], 6)
         print('TC %.4f  TC_sem %.4f  TC_track %.4f' % (100 * r['tc'], 100 * r['tc_sem'], 100 * r['tc_track']))
+    if tc and args.tc_photometric is not None:          # a key of its own: without the option the report is what it was
+        report['tc_photometric'] = dict(thr=args.tc_photometric)
+    if flow_photo:                                      # a key of its own: without the option the report is what it was
+        report['flow_photo'] = photo_report(flow_photo['result'])
+        print('flow photo  MAE warped %.4f  static %.4f  ratio %.4f' % tuple(report['flow_photo'][k] for k in ('mae_warp', 'mae_static', 'ratio')))
     if overlay_video:                                   # a key of its own: without the option the report is what it was
         report['overlay_video'] = dict(files=overlay_video['files'], sampling=args.overlay_video_sampling)
     with open(os.path.join(args.out, 'report.json'), 'w') as f:

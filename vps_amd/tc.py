@@ -61,7 +61,10 @@ not in view stays `outside` whatever the mask says, so in_view + outside + maske
 masked cells and `occluded_share` its share of ALL pixels; `in_view` then counts the visible in-view pixels only and `in_view_share` is
 their share of all pixels. Memory: a second 8 bytes per pixel and frame (the backward flow) until the pair is counted, and one byte
 per pixel for the mask of the pair being counted. What remains a limit: a flow that is wrong but self-consistent in both directions
-is still trusted.
+is still trusted - unless the photometric flag is on too (opt-in: `TcEvaluator(occlusion=True, photometric=THR)`, DESIGN.md 6 row 3h,
+vps_amd/flowphoto.py): the pair's mask then passes through `vps_flow_photo` in place, which gives code 3 to the visible in-view pixels
+whose previous frame, sampled where the flow points, differs from the current frame by more than THR grey levels on average, and the
+counting skips those as well. The `masked` cell then holds occluded plus flagged pixels; the table layout does not change.
 
 `tc_from_tables`, `TcStats` and `tc_text` are NumPy / Python only. The counting (`TcEvaluator`) is `vps_tc_accumulate`
 (csrc/tc_ops.hip): no CPU path, the HIP library must load and a device must be present; host arrays are uploaded, device tensors are
@@ -299,11 +302,22 @@ class TcEvaluator(TcStats):
     class above it, else an id > 0.
     occlusion=True (module docstring): every pair needs its backward flow (`add_pair(.., back_flow=)`, `add_video(.., back_flows=)`);
     the pair's mask is made by `vps_flow_occlusion` with (alpha, beta) and the pair is counted by `vps_tc_accumulate_masked`. Every
-    table row has one more cell (`table_sizes(C, n, occlusion=True)`), still one download per video."""
+    table row has one more cell (`table_sizes(C, n, occlusion=True)`), still one download per video.
+    photometric=THR (with occlusion=True only; vps_amd/flowphoto.py): every pair also needs its two frames
+    (`add_pair(.., frames=(prev_bgr, cur_bgr))`, `add_video(.., frames=)`); between the two launches above the pair's mask goes through
+    `vps_flow_photo` in place, which turns the visible in-view pixels whose photometric warp error is above THR grey levels into code 3,
+    so they are left out of the counts as well: the flow that is wrong but self-consistent in both directions. The tables keep their
+    layout; the masked cell (`occluded`) then holds occluded plus flagged pixels."""
 
     def __init__(self, seg_class, num_classes, id_channel=2, device='cuda', per_pair=False, id_last_stuff=None, occlusion=False, alpha=OCC_ALPHA,
-                 beta=OCC_BETA):
+                 beta=OCC_BETA, photometric=None):
         super().__init__(seg_class, num_classes)
+        if photometric is not None and not occlusion:
+            raise ValueError('photometric= flags pixels in the mask of the occlusion option: it needs occlusion=True')
+        if photometric is not None and not float(photometric) >= 0:
+            raise ValueError('photometric is a threshold in grey levels, not negative, got %r' % (photometric,))
+        self.photometric = None if photometric is None else float(photometric)
+        self._photo = None
         if id_channel not in (1, 2):
             raise ValueError('id_channel is 1 or 2, got %r' % (id_channel,))
         if not (alpha >= 0 and beta >= 0):
@@ -368,10 +382,20 @@ class TcEvaluator(TcStats):
                 return t[i]
             i -= int(t.shape[0])
 
-    def add_pair(self, prev, cur, flow, keys=None, flicker=None, back_flow=None):
+    def _frame(self, f, H, W):
+        t = torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f
+        if not (torch.is_tensor(t) and t.dtype == torch.uint8 and tuple(t.shape) == (H, W, 3)):
+            raise ValueError('frames are uint8 [%d,%d,3] like the maps, got %s %s' % (H, W, getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+        return t.to(self.device).contiguous()
+
+    def add_pair(self, prev, cur, flow, keys=None, flicker=None, back_flow=None, frames=None):
         """count one pair into the open video (opened by the first pair; `keys` then fixes the video's list, None = the thing keys of
         these two maps). flicker: None or a device uint8 [H,W] tensor that receives the inconsistency map. back_flow: the flow from
-        prev to cur, fp32 [H,W,2] - required by an evaluator with occlusion=True, refused by one without. Nothing is downloaded."""
+        prev to cur, fp32 [H,W,2] - required by an evaluator with occlusion=True, refused by one without. frames: (prev_bgr, cur_bgr),
+        the two frames as uint8 [H,W,3] - required by an evaluator with photometric=, refused by one without. Nothing is downloaded."""
+        if (self.photometric is not None) != (frames is not None):
+            raise ValueError('photometric= needs the two frames of every pair (frames=(prev_bgr, cur_bgr))' if frames is None
+                             else 'frames are given but the evaluator was made without photometric=')
         if self.occlusion != (back_flow is not None):
             raise ValueError('occlusion=True needs the backward flow of every pair (back_flow=)' if self.occlusion
                              else 'back_flow is given but the evaluator was made without occlusion=True')
@@ -387,6 +411,8 @@ class TcEvaluator(TcStats):
         if flicker is not None and not (torch.is_tensor(flicker) and flicker.is_cuda and flicker.dtype == torch.uint8 and flicker.is_contiguous()
                                         and tuple(flicker.shape) == (H, W)):
             raise ValueError('flicker is a contiguous device uint8 [H,W] tensor')
+        if frames is not None:
+            fprev, fcur = self._frame(frames[0], H, W), self._frame(frames[1], H, W)
         if self._open is None:
             self._begin(self.video_keys([prev, cur]) if keys is None else keys, 0)
         elif keys is not None and not np.array_equal(np.unique(np.asarray(keys)), self._open['keys']):
@@ -398,6 +424,15 @@ class TcEvaluator(TcStats):
             mask = torch.empty((H, W), dtype=torch.uint8, device=self.device)      # (stream-ordered: the allocator hands the block on only behind its last use)
             hip.check(self.lib.vps_flow_occlusion(hip.ptr(flow), ld, 0, hip.ptr(back_flow), bld, 0, H, W, self.alpha, self.beta, hip.ptr(mask), None,
                                                   hip.stream_ptr()), 'vps_flow_occlusion')
+            if self.photometric is not None:             # in place: the visible pixels that are photometrically wrong become code 3
+                nbytes = int(self.lib.vps_flow_photo_ws_bytes(H, W))
+                hip.check(min(nbytes, 0), 'vps_flow_photo_ws_bytes')
+                if self._photo is None:                  # tables nobody reads: the call wants somewhere to add to
+                    self._photo = (torch.zeros(21, dtype=torch.int64, device=self.device), torch.zeros(4, dtype=torch.float64, device=self.device))
+                ws = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
+                hip.check(self.lib.vps_flow_photo(hip.ptr(fcur), hip.ptr(fprev), H, W, hip.ptr(flow), ld, 0, hip.ptr(mask), self.photometric,
+                                                  hip.ptr(self._photo[0]), hip.ptr(self._photo[1]), hip.ptr(mask), None, hip.ptr(ws), nbytes,
+                                                  hip.stream_ptr()), 'vps_flow_photo')
             hip.check(self.lib.vps_tc_accumulate_masked(hip.ptr(prev), hip.ptr(cur), H, W, hip.ptr(flow), ld, 0, self.id_channel,
                                                         self.seg_class.ctypes.data_as(ctypes.c_void_p), C, hip.ptr(o['d_keys']) if n else None, n,
                                                         hip.ptr(conf), hip.ptr(psz) if n else None, hip.ptr(csz) if n else None,
@@ -426,20 +461,24 @@ class TcEvaluator(TcStats):
         parts = np.split(total, np.cumsum(table_sizes(C, len(o['keys']), self.occlusion))[:-1])
         return self.add_tables(video_id, o['keys'], *parts[:5], pairs=pairs, masked=parts[5] if self.occlusion else None)
 
-    def add_video(self, maps, flows, video_id=None, keys=None, flickers=None, back_flows=None):
+    def add_video(self, maps, flows, video_id=None, keys=None, flickers=None, back_flows=None, frames=None):
         """maps: the unified maps of one video in order, uint8 [H,W,3] host arrays or device tensors; flows: one per map, flows[t] the
         flow of frame t to frame t-1, fp32 [H,W,2] (flows[0] is not used and may be None); flickers: None or one device uint8 [H,W]
         tensor (or None) per map; back_flows (occlusion=True): one per map, back_flows[t] the flow of frame t-1 to frame t (the first
-        is not used). Returns the video's entry."""
+        is not used); frames (photometric=): one uint8 [H,W,3] frame per map. Returns the video's entry."""
         assert self._open is None, 'a video opened by add_pair is not ended'
         if len(flows) != len(maps):
             raise ValueError('one flow per map (the first is not used): %d maps, %d flows' % (len(maps), len(flows)))
         if self.occlusion != (back_flows is not None) or (back_flows is not None and len(back_flows) != len(maps)):
             raise ValueError('occlusion=True takes one backward flow per map (the first is not used), an evaluator without it takes none')
+        if (self.photometric is not None) != (frames is not None) or (frames is not None and len(frames) != len(maps)):
+            raise ValueError('photometric= takes one frame per map, an evaluator without it takes none')
         maps = [self._map(m) for m in maps]
         self._begin(self.video_keys(maps) if keys is None else keys, max(len(maps) - 1, 0))
         for t in range(1, len(maps)):                    # no synchronisation between pairs
             kw = dict(back_flow=back_flows[t]) if self.occlusion else {}
+            if frames is not None:
+                kw['frames'] = (frames[t - 1], frames[t])
             self.add_pair(maps[t - 1], maps[t], flows[t], flicker=None if flickers is None else flickers[t], **kw)
         return self.end_video(video_id)
 
@@ -455,10 +494,13 @@ def score_videos(evaluator, maps, flows, names, nframes_per_video, map_dir=None,
     lives on the device only until then. map_dir (`--tc-map`): the inconsistency map of every pair, painted with `FLICKER_PALETTE`,
     blended over `frames[i]` (BGR uint8 [H,W,3]) by `render_overlay` and written as map_dir/<name>.jpg by a `DeviceJpegWriter`.
     back_flows (an evaluator with occlusion=True): `back_flows[i]` = `flow_between(ref_img, img)` of frame i, emptied entry by entry as
-    `flows` is; occluded pixels are grey in the inconsistency maps. Returns the written file names."""
+    `flows` is; occluded pixels are grey in the inconsistency maps. An evaluator with photometric= gets `frames[i - 1]` and `frames[i]`
+    with every pair (`frames` is then required); the flagged pixels are grey too. Returns the written file names."""
     from .postprocess import DeviceJpegWriter, overlay_name, render_overlay, video_name_of
     assert len(maps) == len(flows) == len(names) and (map_dir is None or (frames is not None and len(frames) == len(maps)))
     assert back_flows is None or len(back_flows) == len(maps)
+    photo = getattr(evaluator, 'photometric', None) is not None
+    assert not photo or (frames is not None and len(frames) == len(maps))
     writer = DeviceJpegWriter(evaluator.device, quality=quality, entropy=entropy) if map_dir is not None else None
     out = []
     try:
@@ -473,7 +515,8 @@ def score_videos(evaluator, maps, flows, names, nframes_per_video, map_dir=None,
                 if back_flows is None:
                     evaluator.add_pair(vm[j - 1], vm[j], flows[v0 + j], keys=keys, flicker=fl)
                 else:
-                    evaluator.add_pair(vm[j - 1], vm[j], flows[v0 + j], keys=keys, flicker=fl, back_flow=back_flows[v0 + j])
+                    kw = dict(frames=(frames[v0 + j - 1], frames[v0 + j])) if photo else {}
+                    evaluator.add_pair(vm[j - 1], vm[j], flows[v0 + j], keys=keys, flicker=fl, back_flow=back_flows[v0 + j], **kw)
                     back_flows[v0 + j] = None
                 flows[v0 + j] = None
                 if writer is not None:
