@@ -807,6 +807,51 @@ int vps_flow_photo(const uint8_t* cur_bgr, const uint8_t* prev_bgr, int H, int W
                    const uint8_t* mask_in, float thr, int64_t* counts, double* sums, uint8_t* mask_out, uint8_t* residual, void* ws,
                    int64_t ws_bytes, void* stream);
 
+/* Illumination-robust flow residual (csrc/flow_census_ops.hip, vps_amd/flowphoto.py): the ternary census warp error of
+ * ONE (cur, prev, flow) triple. The hard ternary census (Stein 2004) as UnFlow (Meister et al. 2018) uses it, RESTATED FROM MEMORY;
+ * UnFlow's soft, differentiable form is not built. Two launches on `stream` (the warp pass, then the census pass on tiles of
+ * vps_flow_census_tile rows x columns); the call does not synchronise, allocate or zero, and no workgroup waits for or reads from another.
+ *   cur_bgr, prev_bgr, flow, flow_ld, flow_coff, mask_in, mask_out, residual   as vps_flow_photo's: any byte alignment of the five byte maps,
+ *                the three flow layouts, mask_out MAY BE THE SAME BUFFER as mask_in, nothing outside the maps is read
+ *   thr          the flag threshold, an integer percent in 0 .. 100 (default of the Python side 25)
+ *   eps          the dead zone of the ternary code in units of g, finite and not negative (default of the Python side 2000.0 = two grey
+ *                levels). Both defaults are parameter defaults with no real footage behind them
+ *   table        DEVICE int64 [2][13], 8-byte aligned, ADDED to: row g for the mask groups g = 0, 1 of vps_flow_photo
+ *   ws           DEVICE workspace, 16-byte aligned, at least vps_flow_census_ws_bytes(H, W) bytes (HOST arithmetic; -1002 for a bad size):
+ *                three fp32 planes (Wg, the grey of cur, the grey of prev), each (H W rounded up to a multiple of 4) floats: 12 bytes
+ *                per pixel
+ * The rule, every fp32 operation rounded on its own (no contraction):
+ *   1. grey: g = 299 R + 587 G + 114 B (byte 0 of a pixel is B, byte 2 is R), an integer in 0 .. 255 000, held as fp32 (exact)
+ *   2. warped grey Wg(p): the in-view rule (step 1) and the corners and weights (step 3) of vps_flow_photo verbatim; the bilinear sample
+ *      of the four corners' greys in fp32: top = g00 + wx*(g01 - g00), bot = g10 + wx*(g11 - g10), Wg = top + wy*(bot - top). A pixel
+ *      that is not in view has no Wg (-1.0f in the workspace)
+ *   3. window: the neighbours q = p + (dx, dy), dx, dy in -3 .. 3, not both zero: 48
+ *   4. code of an image A: code_A(p, q) = +1 if A(q) - A(p) > eps, -1 if it is < -eps, else 0: one fp32 subtraction, two comparisons
+ *   5. warped count: a neighbour counts when q lies in the image and Wg(q) exists; n_w(p) of them, d_w(p) of those with
+ *      code_cur != code_Wg
+ *   6. static count: prev unwarped in the place of Wg; n_s counts every neighbour in the image, d_s as in 5
+ *   7. p is scored when it is in view and n_w(p) >= 1
+ *   8. a scored pixel is flagged when 100 d_w > thr n_w, strictly, in integers
+ *   9. helped when d_w n_s < d_s n_w, hurt when >
+ *  10. table[g][k]: 0 scored pixels; 1, 2 the sums of d_w, n_w; 3, 4 the sums of d_s, n_s over scored pixels; 5, 6, 7 scored pixels with
+ *      100 d_w > 10, 25, 50 n_w; 8 helped; 9 hurt; 10 flagged; 11 not in view; 12 in view with n_w = 0. Cells 0, 11, 12 of both rows
+ *      together grow by H W per call
+ *  11. mask_out[p] = 2 when p is not in view, else mask_in[p] when that is non-zero, else 3 when flagged, else 0
+ *  12. residual[p] = (255 d_w + n_w / 2) / n_w in integer division; 0 for a pixel that is not scored
+ * Determinism: every decision after the codes is an integer one and the table grows by one 64-bit integer atomic per non-zero cell and
+ * workgroup: the same bytes on every call, twice without zeroing is exactly double; there are no floating-point sums and no finishing
+ * launch. Every corner address of prev is clamped to the map and no index is formed from a float before the in-view test has passed.
+ * vps_flow_census_tile (HOST): rows_cols[0], rows_cols[1] = rows and columns of a tile of the census pass (constants of the build, for
+ * tests that put edges on the seams).
+ * Errors before any launch: -1001 cur_bgr, prev_bgr, flow, table or ws NULL; -1002 H or W < 1 or H W >= 2^31; -1003 flow_coff < 0 or
+ * flow_ld < flow_coff + 2; -1004 table not 8-byte aligned, or the flow base not 4-byte aligned; -1005 ws not 16-byte aligned or ws_bytes
+ * too small; -1006 thr outside 0 .. 100; -1007 eps negative, NaN or infinite. */
+int64_t vps_flow_census_ws_bytes(int H, int W);
+int vps_flow_census_tile(int32_t* rows_cols);
+int vps_flow_census(const uint8_t* cur_bgr, const uint8_t* prev_bgr, int H, int W, const float* flow, int flow_ld, int flow_coff,
+                    const uint8_t* mask_in, int thr, float eps, int64_t* table, uint8_t* mask_out, uint8_t* residual, void* ws,
+                    int64_t ws_bytes, void* stream);
+
 /* Boundary PQ / boundary VPQ (csrc/boundary_ops.hip, vps_amd/boundary.py): the boundary band of EVERY segment of a
  * panoptic map in one call, the device form of Boundary IoU's mask_to_boundary (Cheng et al., CVPR 2021) applied per segment.
  *   pan_rgb   DEVICE uint8 [H][W][3] panoptic map (segment id = R + 256 G + 65536 B, the maps vps_pair_count reads); any byte alignment,

@@ -93,6 +93,15 @@ def parse_args(argv=None):
                     'photometric residual blended over the frame')
     ap.add_argument('--tc-photometric', type=float, default=None, metavar='THR', help='--tc-occlusion, and pixels that are in view and not occluded but whose '
                     'photometric warp error is above THR grey levels are left out of the counts too (they are part of OCC then; off by default)')
+    ap.add_argument('--flow-census', action='store_true', help='illumination-robust flow quality without ground truth (vps_amd.flowphoto, DESIGN.md 6 row '
+                    '3i), also with --video: the ternary census residual of every frame\'s flow between the frame and the previous one of its video, '
+                    'beside the static one of not warping; flow-census.txt and flow-census.json beside pred.json (as --flow-photo; flagged above '
+                    '--tc-census if given, else 25 percent; off by default)')
+    ap.add_argument('--flow-census-map', default=None, metavar='DIR', help='--flow-census: write DIR/<name>.jpg for every frame but a video\'s first, the '
+                    'census residual blended over the frame')
+    ap.add_argument('--tc-census', type=int, default=None, metavar='THR', help='--tc-occlusion, and pixels that are in view and not occluded but whose '
+                    'census residual is above THR percent of their counted neighbours are left out of the counts too (they are part of OCC then; may '
+                    'be combined with --tc-photometric; off by default)')
     ap.add_argument('--dry-size', default='128x256'); ap.add_argument('--dry-videos', type=int, default=1); ap.add_argument('--dry-frames', type=int, default=16)
     ap.add_argument('--check-only', action='store_true')
     return ap.parse_args(argv)
@@ -224,10 +233,12 @@ def run(args, tmp):
     model.ensure_packed(dev)
     prep = DeviceImagePrep(**cfg.img_norm_cfg, size_divisor=32, img_scale=(2048, 1024), device=dev)
     files = [os.path.join(img_prefix, x['file_name']) for x in info]
-    if args.tc_photometric is not None:
+    if args.tc_photometric is not None or args.tc_census is not None:
         args.tc_occlusion = True
     with_photo = bool(args.flow_photo or args.flow_photo_map)
-    keep = bool(args.overlay or args.overlay_video or args.tc_map or with_photo or args.tc_photometric is not None)
+    with_census = bool(args.flow_census or args.flow_census_map)
+    keep = bool(args.overlay or args.overlay_video or args.tc_map or with_photo or with_census or args.tc_photometric is not None
+                or args.tc_census is not None)
     with_tc = bool(args.tc or args.tc_map or args.tc_occlusion)
     if reader is not None:
         assert len(reader) > 0, '%s holds no complete frame' % args.video
@@ -240,7 +251,7 @@ def run(args, tmp):
         from vps_amd.flowvis import FlowWriter, flow_name
         model.keep_flow = True
         flow_writer = FlowWriter(dev, fmt=args.flow_format, max_rad=args.flow_max_rad, entropy=args.jpeg_entropy)
-    if with_tc or with_photo:
+    if with_tc or with_photo or with_census:
         model.keep_flow = True
         res['all_flows'] = []
     if args.tc_occlusion:
@@ -265,7 +276,7 @@ def run(args, tmp):
                 res['all_frames'].append(feeder.frame(idx))       # the decoded BGR frame the feeder holds anyway
             if flow_writer is not None:
                 flow_writer.submit(result[2]['flow'], flow_name(args.flow, files[idx], args.flow_format))
-            if with_tc or with_photo:
+            if with_tc or with_photo or with_census:
                 res['all_flows'].append(result[2]['flow'])
             if args.tc_occlusion:                            # the flow from the previous frame to this one: a second FlowNet2 pass, behind the frame
                 res['all_back_flows'].append(model.flow_between(ref, img, img_shape=meta['img_shape']) if idx % span > 0 else None)
@@ -318,13 +329,32 @@ def run(args, tmp):
         pr['map_files'] = pfiles
         report['flow_photo'] = dict(photo_report(pr), file=os.path.join(output_dir, 'flow-photo.txt'))
         print('flow photo  MAE warped %.4f  static %.4f  ratio %.4f' % tuple(report['flow_photo'][k] for k in ('mae_warp', 'mae_static', 'ratio')))
+    if with_census:                                         # a key of its own: without the options the report is what it was
+        from run_vps_synthetic import census_report
+        from vps_amd import flowphoto
+        order = sorted(range(len(res['all_names'])), key=lambda i: res['all_names'][i])                # the order of pred_pans_2ch
+        cev = flowphoto.CensusEvaluator(dev, thr=flowphoto.CENSUS_THR if args.tc_census is None else args.tc_census, per_pair=True)
+        cfiles = flowphoto.score_videos(cev, [res['all_frames'][i] for i in order], [res['all_flows'][i] for i in order], [res['all_names'][i] for i in order],
+                                        span, back_flows=[res['all_back_flows'][i] for i in order] if args.tc_occlusion else None,
+                                        map_dir=args.flow_census_map, alpha=args.overlay_alpha, quality=args.overlay_quality, entropy=args.jpeg_entropy)
+        cr = cev.result()
+        flowphoto.write_census_outputs(cr, output_dir)
+        cr['map_files'] = cfiles
+        report['flow_census'] = dict(census_report(cr), file=os.path.join(output_dir, 'flow-census.txt'))
+        print('flow census  CE warped %.4f  static %.4f  ratio %.4f' % tuple(report['flow_census'][k] for k in ('ce_warp', 'ce_static', 'ratio')))
     if with_tc:                                             # a key of its own: without the options the report is what it was
         from vps_amd import tc
         nseg = 19                                           # PanopticUnifier(dev, 19, 9): the 19 classes are their own indices, the rest is void
         seg_class = np.full(256, 255, dtype=np.uint8)
         seg_class[:nseg] = np.arange(nseg)
         okw = {}
-        if args.tc_photometric is not None:
+        if args.tc_census is not None:
+            ev = tc.TcEvaluator(seg_class, nseg, id_channel=2, device=dev, per_pair=True, id_last_stuff=unifier.id_last_stuff, occlusion=True,
+                                photometric=args.tc_photometric, census=args.tc_census)
+            report['tc_census'] = dict(thr=args.tc_census, eps=ev.census_eps)
+            if args.tc_photometric is not None:
+                report['tc_photometric'] = dict(thr=args.tc_photometric)
+        elif args.tc_photometric is not None:
             ev = tc.TcEvaluator(seg_class, nseg, id_channel=2, device=dev, per_pair=True, id_last_stuff=unifier.id_last_stuff, occlusion=True,
                                 photometric=args.tc_photometric)
             report['tc_photometric'] = dict(thr=args.tc_photometric)
@@ -339,7 +369,7 @@ def run(args, tmp):
             okw['back_flows'] = [res['all_back_flows'][i] for i in order]
             res['all_back_flows'] = None
         tfiles = tc.score_videos(ev, pred_pans_2ch, flows, [res['all_names'][i] for i in order], span, map_dir=args.tc_map,
-                                 frames=[res['all_frames'][i] for i in order] if (args.tc_map or args.tc_photometric is not None) else None,
+                                 frames=[res['all_frames'][i] for i in order] if (args.tc_map or args.tc_photometric is not None or args.tc_census is not None) else None,
                                  alpha=args.overlay_alpha,
                                  quality=args.overlay_quality, entropy=args.jpeg_entropy, **okw)
         r = ev.result()

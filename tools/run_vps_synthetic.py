@@ -117,7 +117,7 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg
 
 
 def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_png=False, overlay=None, tubes=False, jpeg_entropy='host',
-                overlay_video=None, tc=None, flow_photo=None):
+                overlay_video=None, tc=None, flow_photo=None, flow_census=None):
     """test_vpq.py:178-198 with the device-side unifier / converter / asynchronous writer (`device_png`: the PNGs are filtered and
     deflated on the device too, postprocess.DevicePngWriter). `overlay` = (directory, quality, alpha): an overlay JPEG of EVERY frame,
     blended and transformed on the device (postprocess.write_overlays). `tubes`: tubes.json beside pred.json, the COCO run-length
@@ -128,7 +128,9 @@ def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_pn
     is given; with 'occlusion' the forward-backward check on res['all_back_flows'] first; with 'photometric' = THR the photometric flag of
     vps_amd.flowphoto on top of it); its 'result' entry receives the figures. `flow_photo` = dict(map_dir, thr, alpha, quality): the
     photometric warp error of the run's own flows between the decoded frames (vps_amd.flowphoto; flow-photo.txt and flow-photo.json
-    beside pred.json, the residual overlays in map_dir if it is given), before `tc` lets the flows go; its 'result' entry likewise"""
+    beside pred.json, the residual overlays in map_dir if it is given), before `tc` lets the flows go; its 'result' entry likewise.
+    `flow_census` = dict(map_dir, thr, eps, alpha, quality): the same with the ternary census residual (flow-census.txt and
+    flow-census.json); tc['census'] = THR is the census flag of the temporal consistency"""
     from vps_amd.postprocess import DevicePngWriter, PanopticUnifier, inference_panoptic_video, write_overlays
     unifier = PanopticUnifier(dev, 19, 9)
     two = unifier.get_unified_pan_result(res['all_ssegs'], res['all_panos'], res['all_pano_cls_inds'], obj_ids=res['all_pano_obj_ids'],
@@ -137,6 +139,8 @@ def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_pn
     pred_pans_2ch = [two[k] for k in keys]
     if flow_photo is not None:
         flow_photo['result'] = photo_score(pred_pans_2ch, res, keys, len(keys) // max(videos, 1), dev, out_dir, flow_photo, jpeg_entropy)
+    if flow_census is not None:
+        flow_census['result'] = census_score(pred_pans_2ch, res, keys, len(keys) // max(videos, 1), dev, out_dir, flow_census, jpeg_entropy)
     if tc is not None:
         tc['result'] = tc_score(pred_pans_2ch, res, keys, len(keys) // max(videos, 1), dev, out_dir, unifier.id_last_stuff, tc, jpeg_entropy)
     names = keys[(labeled_fid // lambda_)::lambda_]                               # names of the labelled frames (im_jsons['images'])
@@ -187,6 +191,31 @@ def photo_score(maps, res, names, nframes_per_video, dev, out_dir, opt, jpeg_ent
     return result
 
 
+def census_score(maps, res, names, nframes_per_video, dev, out_dir, opt, jpeg_entropy='host'):
+    """--flow-census: `photo_score` with the ternary census residual (`flowphoto.CensusEvaluator`) in the place of the photometric error"""
+    from vps_amd import flowphoto
+    at = {n: i for i, n in enumerate(res['all_names'])}
+    ev = flowphoto.CensusEvaluator(dev, thr=opt['thr'], eps=opt['eps'], per_pair=True)
+    back = [res['all_back_flows'][at[n]] for n in names] if res.get('all_back_flows') is not None else None
+    files = flowphoto.score_videos(ev, padded_frames(res, names, maps), [res['all_flows'][at[n]] for n in names], names, nframes_per_video, back_flows=back,
+                                   map_dir=opt.get('map_dir'), alpha=opt.get('alpha', 128), quality=opt.get('quality', 90), entropy=jpeg_entropy)
+    result = ev.result()
+    flowphoto.write_census_outputs(result, out_dir)
+    result['map_files'] = files
+    return result
+
+
+def census_report(r):
+    """the 'flow_census' entry of the report from the result of `flowphoto.CensusEvaluator`"""
+    a = r['all']
+    out = dict(thr=r['thr'], eps=r['eps'], pairs=r['pairs'], ce_warp=round(a['ce_warp'], 6), ce_static=round(a['ce_static'], 6), ratio=round(a['ratio'], 6),
+               gain=round(a['gain'], 6), flagged_share=round(a['flagged_share'], 6), outside_share=round(a['outside_share'], 6),
+               map_files=len(r['map_files']))
+    if r['masked']['n']:
+        out.update(ce_warp_visible=round(r['visible']['ce_warp'], 6), ce_warp_masked=round(r['masked']['ce_warp'], 6))
+    return out
+
+
 def tc_score(maps, res, names, nframes_per_video, dev, out_dir, id_last_stuff, opt, jpeg_entropy='host'):
     """--tc: the unified maps of every frame (in the order of `names`) against their predecessors warped by the run's own flows. The 19
     classes of CATEGORIES are the class indices, every other pan_seg value is void; tracks are keyed by pan_obj (channel 2)"""
@@ -194,7 +223,10 @@ def tc_score(maps, res, names, nframes_per_video, dev, out_dir, id_last_stuff, o
     seg_class = np.full(256, 255, dtype=np.uint8)
     seg_class[:len(CATEGORIES)] = np.arange(len(CATEGORIES))
     kw = {}
-    if opt.get('photometric') is not None:                # --tc-photometric: occluded and photometrically wrong pixels are left out of the counts
+    if opt.get('census') is not None:                     # --tc-census: occluded pixels and pixels the census flags are left out of the counts
+        ev = tc.TcEvaluator(seg_class, len(CATEGORIES), id_channel=2, device=dev, per_pair=True, id_last_stuff=id_last_stuff, occlusion=True,
+                            photometric=opt.get('photometric'), census=opt['census'], census_eps=opt.get('census_eps'))
+    elif opt.get('photometric') is not None:              # --tc-photometric: occluded and photometrically wrong pixels are left out of the counts
         ev = tc.TcEvaluator(seg_class, len(CATEGORIES), id_channel=2, device=dev, per_pair=True, id_last_stuff=id_last_stuff, occlusion=True,
                             photometric=opt['photometric'])
     elif opt.get('occlusion'):                            # --tc-occlusion: occluded pixels are left out of the counts
@@ -208,7 +240,7 @@ def tc_score(maps, res, names, nframes_per_video, dev, out_dir, id_last_stuff, o
         kw['back_flows'] = [res['all_back_flows'][at[n]] for n in names]
         res['all_back_flows'] = None
     frames = None
-    if opt.get('map_dir') or opt.get('photometric') is not None:
+    if opt.get('map_dir') or opt.get('photometric') is not None or opt.get('census') is not None:
         frames = padded_frames(res, names, maps)
     files = tc.score_videos(ev, maps, flows, names, nframes_per_video, map_dir=opt.get('map_dir'), frames=frames, alpha=opt.get('alpha', 128),
                             quality=opt.get('quality', 90), entropy=jpeg_entropy, **kw)
@@ -319,6 +351,17 @@ def parse_args(argv=None):
                     'photometric residual blended over the frame')
     ap.add_argument('--tc-photometric', type=float, default=None, metavar='THR', help='--tc-occlusion, and pixels that are in view and not occluded but whose '
                     'photometric warp error is above THR grey levels are left out of the counts too (they are part of OCC then; off by default)')
+    ap.add_argument('--flow-census', action='store_true', help='illumination-robust flow quality without ground truth (vps_amd.flowphoto, DESIGN.md 6 row '
+                    '3i): the ternary census residual of every frame\'s flow between the frame and the previous one, beside the static one of not '
+                    'warping; pred/flow-census.txt and pred/flow-census.json (as --flow-photo; flagged above --tc-census if given, else 25 percent; '
+                    'off by default)')
+    ap.add_argument('--flow-census-map', default=None, metavar='DIR', help='--flow-census: write DIR/<name>.jpg for every frame but a video\'s first, the '
+                    'census residual blended over the frame')
+    ap.add_argument('--tc-census', type=int, default=None, metavar='THR', help='--tc-occlusion, and pixels that are in view and not occluded but whose '
+                    'census residual is above THR percent of their counted neighbours are left out of the counts too (they are part of OCC then; may '
+                    'be combined with --tc-photometric; off by default)')
+    ap.add_argument('--flow-census-eps', type=float, default=None, metavar='EPS', help='--flow-census / --tc-census: the dead zone of the ternary code in '
+                    'thousandths of a grey level (default 2000 = two grey levels)')
     return ap.parse_args(argv)
 
 
@@ -330,23 +373,30 @@ def main(argv=None):
     overlay_video = dict(file=args.overlay_video, sampling=args.overlay_video_sampling, files=[], alpha=args.overlay_alpha) if args.overlay_video else None
     nper = len(range(labeled_fid // lambda_, args.frames, lambda_))
     flow = (args.flow, args.flow_format, args.flow_max_rad) if args.flow else None
-    if args.tc_photometric is not None:
+    if args.tc_photometric is not None or args.tc_census is not None:
         args.tc_occlusion = True
     tc = dict(map_dir=args.tc_map, alpha=args.overlay_alpha, quality=args.overlay_quality) if (args.tc or args.tc_map or args.tc_occlusion) else None
     if tc and args.tc_occlusion:
         tc['occlusion'] = True
     if tc and args.tc_photometric is not None:
         tc['photometric'] = args.tc_photometric
+    if tc and args.tc_census is not None:
+        tc['census'], tc['census_eps'] = args.tc_census, args.flow_census_eps
+    flow_census = None
+    if args.flow_census or args.flow_census_map:
+        from vps_amd.flowphoto import CENSUS_EPS, CENSUS_THR
+        flow_census = dict(map_dir=args.flow_census_map, thr=CENSUS_THR if args.tc_census is None else args.tc_census,
+                           eps=CENSUS_EPS if args.flow_census_eps is None else args.flow_census_eps, alpha=args.overlay_alpha, quality=args.overlay_quality)
     flow_photo = None
     if args.flow_photo or args.flow_photo_map:
         from vps_amd.flowphoto import PHOTO_THR
         flow_photo = dict(map_dir=args.flow_photo_map, thr=PHOTO_THR if args.tc_photometric is None else args.tc_photometric, alpha=args.overlay_alpha,
                           quality=args.overlay_quality)
     res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated, flow, args.jpeg_entropy,
-                        keep_flows=tc is not None or flow_photo is not None, back_flows=args.tc_occlusion)
+                        keep_flows=tc is not None or flow_photo is not None or flow_census is not None, back_flows=args.tc_occlusion)
     t0 = time.perf_counter()
     names, pans, pj = postprocess(res, os.path.join(args.out, 'pred'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png, overlay, args.tubes,
-                                  args.jpeg_entropy, overlay_video, tc, flow_photo)
+                                  args.jpeg_entropy, overlay_video, tc, flow_photo, flow_census)
     dpost = time.perf_counter() - t0
     pred = (pans, pj)
     gt = pred
@@ -387,6 +437,12 @@ def main(argv=None):
     if flow_photo:                                      # a key of its own: without the option the report is what it was
         report['flow_photo'] = photo_report(flow_photo['result'])
         print('flow photo  MAE warped %.4f  static %.4f  ratio %.4f' % tuple(report['flow_photo'][k] for k in ('mae_warp', 'mae_static', 'ratio')))
+    if tc and args.tc_census is not None:               # a key of its own: without the option the report is what it was
+        from vps_amd.flowphoto import CENSUS_EPS
+        report['tc_census'] = dict(thr=args.tc_census, eps=CENSUS_EPS if args.flow_census_eps is None else args.flow_census_eps)
+    if flow_census:                                     # a key of its own: without the option the report is what it was
+        report['flow_census'] = census_report(flow_census['result'])
+        print('flow census  CE warped %.4f  static %.4f  ratio %.4f' % tuple(report['flow_census'][k] for k in ('ce_warp', 'ce_static', 'ratio')))
     if overlay_video:                                   # a key of its own: without the option the report is what it was
         report['overlay_video'] = dict(files=overlay_video['files'], sampling=args.overlay_video_sampling)
     with open(os.path.join(args.out, 'report.json'), 'w') as f:

@@ -90,6 +90,17 @@ PX4_FN uint32_t px4_load_bytes(const uint8_t* __restrict__ p, long npix, long p0
     return r;
 }
 
+// bytes p0 .. p0 + n - 1 of a byte map for ANY p0 (the 4 pixels of a lane inside a tile row), byte i in bits 8 i: one dword where the
+// address p + p0 is dword-aligned and the chunk is whole, byte by byte otherwise. Only the n bytes themselves are read either way.
+PX4_FN uint32_t px4_load_bytes_at(const uint8_t* __restrict__ p, long p0, int n) {
+    if (n == PX4 && ((uintptr_t)(p + p0) & 3) == 0) return *reinterpret_cast<const px4_u32*>(p + p0);
+    uint32_t r = 0;
+#pragma unroll
+    for (int i = 0; i < PX4; ++i)
+        if (i < n) r |= (uint32_t)p[p0 + i] << (8 * i);
+    return r;
+}
+
 // the other way: byte i of `codes` to dst[p0 + i], as one dword where dst is dword-aligned (dst4) and the chunk is whole
 PX4_FN void px4_store_bytes(uint8_t* __restrict__ dst, bool dst4, long p0, int n, uint32_t codes) {
     if (dst4 && n == PX4) {

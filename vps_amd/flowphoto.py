@@ -46,7 +46,37 @@ charged to the flow; a flow can match the colours of the wrong place (flat regio
 
 `photo_from_tables`, `PhotoStats`, `photo_text` are NumPy / Python only. The counting (`flow_photometric`, `PhotoEvaluator`) is
 `vps_flow_photo`: no CPU path, the HIP library must load and a device must be present; host arrays are uploaded, device tensors are
-used where they lie. The sums are reproducible byte for byte: no floating-point atomics (include/vps_hip.h)."""
+used where they lie. The sums are reproducible byte for byte: no floating-point atomics (include/vps_hip.h).
+
+The ternary census residual (`vps_flow_census`, csrc/flow_census_ops.hip) is the illumination-robust twin of the
+above, opt-in: the hard ternary census (Stein, "Efficient computation of optical flow using the census transform", 2004) as UnFlow
+(Meister et al., AAAI 2018) uses it, RESTATED FROM MEMORY; UnFlow's soft, differentiable form is not built. It compares the ordering of
+each pixel against its 7 x 7 neighbourhood, not the intensities: an additive brightness change cancels exactly, a moderate gain change
+too. `CENSUS_EPS` and `CENSUS_THR` are parameter defaults with NO real footage behind them. Inputs as above. The rule:
+    1. grey            g = 299 R + 587 G + 114 B of a BGR pixel, an integer in 0 .. 255 000, held as fp32 (exact)
+    2. warped grey     Wg(p): the in-view rule of step 1 above and the corners and weights of step 3 above, verbatim; the bilinear sample
+                       of the four corners' greys in fp32 in that order (top, bot, then s), every operation rounded on its own. A pixel
+                       that is not in view has no Wg
+    3. window          the neighbours q = p + (dx, dy), dx, dy in -3 .. 3, not both zero: 48
+    4. code            for an image A: code_A(p, q) = +1 if A(q) - A(p) > eps, -1 if it is < -eps, else 0: one fp32 subtraction and two
+                       comparisons; eps is fp32 in units of g (`CENSUS_EPS` = 2000.0: two grey levels)
+    5. warped count    a neighbour counts when q lies in the image and Wg(q) exists: n_w(p) of them, d_w(p) of those with
+                       code_cur != code_Wg
+    6. static count    prev unwarped in the place of Wg: n_s counts every neighbour in the image, d_s as in 5
+    7. scored          p is in view and n_w(p) >= 1
+    8. flagged         a scored pixel with 100 d_w > thr n_w, thr an integer percent in 0 .. 100 (`CENSUS_THR` = 25), strictly, in integers
+    9. helped / hurt   d_w n_s < d_s n_w / d_w n_s > d_s n_w
+   10. table           int64 [2][13] (`CENSUS_CELLS`), row g as in step 2 above (also for the pixels that are not scored): 0 scored pixels,
+                       1 / 2 the sums of d_w / n_w, 3 / 4 the sums of d_s / n_s over scored pixels, 5 / 6 / 7 scored pixels with
+                       100 d_w > 10 / 25 / 50 n_w, 8 helped, 9 hurt, 10 flagged, 11 not in view, 12 in view with n_w = 0. Cells 0, 11
+                       and 12 of both rows together grow by H W per pair. Integer adds only: twice without zeroing is exactly double
+   11. mask_out[p]     2 when p is not in view, else mask[p] when that is non-zero, else 3 when flagged, else 0
+   12. residual[p]     (255 d_w + n_w / 2) / n_w in integer division; 0 for a pixel that is not scored
+Figures (`census_from_tables`), per group and overall, every quotient 0 when its denominator is 0: ce_warp = sum d_w / sum n_w,
+ce_static = sum d_s / sum n_s, ratio = ce_warp / ce_static, gain = ce_static - ce_warp, above_10 / above_25 / above_50, helped, hurt,
+flagged_share (shares of the scored pixels), outside (cell 11), alone (cell 12), outside_share = outside / (n + outside + alone).
+`census_from_tables`, `CensusStats`, `census_text` are NumPy / Python only; `flow_census` and `CensusEvaluator` are `vps_flow_census`:
+no CPU path."""
 import json
 import math
 import os
@@ -61,6 +91,11 @@ COUNT_CELLS, SUM_CELLS = 21, 4
 PHOTO_THR = 16.0                                         # grey levels; a parameter default with no real footage behind it
 LEVELS = (4, 8, 16, 32)
 GROUPS = ('visible', 'masked')
+CENSUS_CELLS = 13
+CENSUS_EPS = 2000.0                                      # units of g (two grey levels); a parameter default with no real footage behind it
+CENSUS_THR = 25                                          # percent of the counted neighbours; a parameter default with no real footage behind it
+CENSUS_LEVELS = (10, 25, 50)
+CENSUS_FIGURES = ('ce_warp', 'ce_static', 'ratio', 'gain', 'above_10', 'above_25', 'above_50', 'helped', 'hurt', 'flagged_share', 'outside_share')
 FIGURES = ('mae_warp', 'rms_warp', 'psnr_warp', 'mae_static', 'rms_static', 'psnr_static', 'ratio', 'gain_db', 'above_4', 'above_8', 'above_16',
            'above_32', 'helped', 'hurt', 'flagged_share')
 
@@ -346,4 +381,183 @@ def write_outputs(result, out_dir):
     with open(os.path.join(out_dir, 'flow-photo.txt'), 'w') as f:
         f.write(photo_text(result))
     with open(os.path.join(out_dir, 'flow-photo.json'), 'w') as f:
+        json.dump(result, f, indent=1)
+
+
+# ---------------------------------------------------------------------------------------------- the ternary census residual (row 3i)
+def _census_figures(c):
+    """one row of the table (or the sum of both) -> its figures"""
+    n = int(c[0])
+    out = {'n': n, 'ce_warp': _q(c[1], c[2]), 'ce_static': _q(c[3], c[4])}
+    out['ratio'] = _q(out['ce_warp'], out['ce_static'])
+    out['gain'] = out['ce_static'] - out['ce_warp']
+    for i, lv in enumerate(CENSUS_LEVELS):
+        out['above_%d' % lv] = _q(c[5 + i], n)
+    out.update(helped=_q(c[8], n), hurt=_q(c[9], n), flagged=int(c[10]), flagged_share=_q(c[10], n), outside=int(c[11]), alone=int(c[12]))
+    out['outside_share'] = _q(out['outside'], n + out['outside'] + out['alone'])
+    return out
+
+
+def census_from_tables(table):
+    """One pair's or one set's int64 [2][13] table -> {'all': figures, 'visible': figures of row 0, 'masked': figures of row 1} as plain
+    Python numbers; 'all' is the two rows added."""
+    t = np.asarray(table, dtype=np.int64).reshape(2, CENSUS_CELLS)
+    return {'all': _census_figures(t[0] + t[1]), 'visible': _census_figures(t[0]), 'masked': _census_figures(t[1])}
+
+
+def _census_args(thr, eps):
+    if not (isinstance(thr, (int, np.integer)) and not isinstance(thr, bool) and 0 <= int(thr) <= 100):
+        raise ValueError('thr is an integer percent in 0 .. 100, got %r' % (thr,))
+    if not (math.isfinite(float(eps)) and float(eps) >= 0):
+        raise ValueError('eps is finite and not negative, got %r' % (eps,))
+    return int(thr), float(eps)
+
+
+class CensusStats:
+    """Host side of the census evaluation: collects the downloaded tables of every video and turns them into the result. No device."""
+
+    def __init__(self, thr=CENSUS_THR, eps=CENSUS_EPS):
+        self.thr, self.eps = _census_args(thr, eps)
+        self.table = np.zeros((2, CENSUS_CELLS), dtype=np.int64)
+        self.videos = []
+        self.npairs = 0
+
+    def add_tables(self, video_id, table, npairs=1):
+        """one video's table: int64 [2][13] of `npairs` pairs together, or [npairs][2][13], one per pair"""
+        table = np.asarray(table, dtype=np.int64)
+        pairs = None
+        if table.ndim == 3:
+            assert table.shape == (npairs, 2, CENSUS_CELLS), table.shape
+            pairs = [dict(census_from_tables(table[i]), pair=i + 1) for i in range(npairs)]
+            vt = table.sum(0)
+        else:
+            vt = table.reshape(2, CENSUS_CELLS).copy()
+        self.table += vt
+        self.npairs += npairs
+        st = dict(census_from_tables(vt), video=len(self.videos) if video_id is None else video_id, pairs=npairs, table=vt, per_pair=pairs)
+        self.videos.append(st)
+        return st
+
+    def result(self):
+        """`census_from_tables` of the set with 'thr', 'eps', 'pairs', 'table' (as lists), 'per_video' and 'per_pair' (for the videos
+        counted with per-pair rows): plain Python numbers, lists and strings"""
+        res = census_from_tables(self.table)
+        keep = ('all', 'visible', 'masked')
+        res.update(thr=self.thr, eps=self.eps, pairs=self.npairs, table=[[int(v) for v in row] for row in self.table],
+                   per_video=[dict({k: st[k] for k in keep}, video=st['video'], pairs=st['pairs']) for st in self.videos],
+                   per_pair=[dict({k: p[k] for k in keep}, video=st['video'], pair=p['pair']) for st in self.videos for p in (st['per_pair'] or [])])
+        return res
+
+
+def census_text(result):
+    """the text of flow-census.txt: per video and for the set one row per group (all, visible, masked) - the scored pixels, the census
+    error warped and static, their ratio and gain, the shares x100 above 10 / 25 / 50 percent, helped, hurt and flagged, and the pixels
+    not in view and in view without a counted neighbour"""
+    width = 124
+    head = '{:16s}| {:8s} {:>11s} {:>7s} {:>7s} {:>6s} {:>7s} {:>6s} {:>6s} {:>6s} {:>6s} {:>6s} {:>6s} {:>10s} {:>8s}'.format(
+        'VIDEO', 'GROUP', 'N', 'CE-w', 'CE-s', 'RATIO', 'GAIN', '>10', '>25', '>50', 'HELP', 'HURT', 'FLAG', 'OUTSIDE', 'ALONE')
+
+    def rows(name, r):
+        out = []
+        for grp in ('all',) + GROUPS:
+            f = r[grp]
+            out.append('{:16s}| {:8s} {:11d} {:7.4f} {:7.4f} {:6.3f} {:7.4f} {:6.2f} {:6.2f} {:6.2f} {:6.2f} {:6.2f} {:6.2f} {:10d} {:8d}'.format(
+                name[:16], grp, f['n'], f['ce_warp'], f['ce_static'], f['ratio'], f['gain'], 100 * f['above_10'], 100 * f['above_25'],
+                100 * f['above_50'], 100 * f['helped'], 100 * f['hurt'], 100 * f['flagged_share'], f['outside'], f['alone']))
+        return out
+    out = ['=' * width, head, '-' * width]
+    for r in result.get('per_video', []):
+        out += rows(str(r['video']), r)
+    out += ['-' * width] + rows('All (%d)' % result['pairs'], result)
+    out.append('thr {:d} %  eps {:g}  outside {:.2f} %'.format(result['thr'], result['eps'], 100 * result['all']['outside_share']))
+    return '\n'.join(out) + '\n'
+
+
+def _census_accumulate(lib, cur, prev, flow, mask, thr, eps, table, mask_out, residual, device):
+    thr, eps = _census_args(thr, eps)
+    flow, ld = _flow_layout(flow, device)
+    H, W = int(flow.shape[0]), int(flow.shape[1])
+    cur, prev = _frame(cur, H, W, device, 'cur'), _frame(prev, H, W, device, 'prev')
+    if mask is not None:
+        m = torch.from_numpy(np.ascontiguousarray(mask)) if isinstance(mask, np.ndarray) else mask
+        if not (torch.is_tensor(m) and m.dtype == torch.uint8 and tuple(m.shape) == (H, W)):
+            raise ValueError('mask is uint8 [%d,%d] like the flow, got %s %s' % (H, W, getattr(m, 'dtype', type(m)), tuple(getattr(m, 'shape', ()))))
+        mask = m if (m.is_cuda and m.is_contiguous()) else m.to(device).contiguous()     # (a device mask is used where it lies: it may be mask_out)
+    _out_map(mask_out, H, W, 'mask_out')
+    _out_map(residual, H, W, 'residual')
+    nbytes = int(lib.vps_flow_census_ws_bytes(H, W))
+    hip.check(min(nbytes, 0), 'vps_flow_census_ws_bytes')
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=device)            # (stream-ordered: the allocator hands the block on only behind its last use)
+    hip.check(lib.vps_flow_census(hip.ptr(cur), hip.ptr(prev), H, W, hip.ptr(flow), ld, 0, hip.ptr(mask), thr, eps, hip.ptr(table), hip.ptr(mask_out),
+                                  hip.ptr(residual), hip.ptr(ws), nbytes, hip.stream_ptr()), 'vps_flow_census')
+
+
+def flow_census(cur, prev, flow, mask=None, thr=CENSUS_THR, eps=CENSUS_EPS, table=None, mask_out=None, residual=None):
+    """One pair through `vps_flow_census` on the current stream; nothing is downloaded or synchronised. The arguments of
+    `flow_photometric`; thr: an integer percent in 0 .. 100, eps in units of g. table: None (a fresh zeroed table) or a contiguous device
+    int64 [2,13] tensor the call ADDS to. mask_out may be `mask` itself. -> table."""
+    if not (torch.is_tensor(flow) and flow.is_cuda):
+        raise hip.VpsHipError('flow_census runs on the device (vps_flow_census); there is no CPU path')
+    dev = flow.device
+    if table is None:
+        table = torch.zeros((2, CENSUS_CELLS), dtype=torch.int64, device=dev)
+    elif not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.numel() == 2 * CENSUS_CELLS):
+        raise ValueError('table is a contiguous device int64 [2,%d] tensor' % CENSUS_CELLS)
+    _census_accumulate(hip.load(), cur, prev, flow, mask, thr, eps, table, mask_out, residual, dev)
+    return table
+
+
+class CensusEvaluator(CensusStats):
+    """The device side. `add_pair` counts one pair into a table that stays on the device (`vps_flow_census`, no synchronisation between
+    pairs); `end_video` is the ONE download of a video. per_pair=True: every pair gets its own table (in blocks of 16, still one
+    download), the video's table is their sum and `result()['per_pair']` has the figures of every pair."""
+
+    def __init__(self, device='cuda', thr=CENSUS_THR, eps=CENSUS_EPS, per_pair=False):
+        super().__init__(thr, eps)
+        self.device = _device(device)
+        self.per_pair = bool(per_pair)
+        self.lib = hip.load()
+        self._tables, self._n = [], 0
+
+    def _row(self):
+        i = self._n if self.per_pair else 0
+        if i >= 16 * len(self._tables):
+            self._tables.append(torch.zeros((16 if self.per_pair else 1, 2, CENSUS_CELLS), dtype=torch.int64, device=self.device))
+        return self._tables[i // 16][i % 16]
+
+    def add_pair(self, prev_frame, cur_frame, flow, mask=None, residual=None):
+        """count one pair into the open video (opened by the first pair); the arguments of `PhotoEvaluator.add_pair`"""
+        _census_accumulate(self.lib, cur_frame, prev_frame, flow, mask, self.thr, self.eps, self._row(), None, residual, self.device)
+        self._n += 1
+
+    def end_video(self, video_id=None):
+        """the one download (and synchronisation) of the open video; returns its entry"""
+        assert self._n, 'no video is open'
+        tables = (torch.cat(self._tables) if len(self._tables) > 1 else self._tables[0]).cpu().numpy()
+        n = self._n
+        self._tables, self._n = [], 0
+        return self.add_tables(video_id, tables[:n] if self.per_pair else tables[0], n)
+
+    def add_video(self, frames, flows, video_id=None, masks=None, residuals=None):
+        """as `PhotoEvaluator.add_video`"""
+        assert self._n == 0, 'a video opened by add_pair is not ended'
+        if len(flows) != len(frames) or any(x is not None and len(x) != len(frames) for x in (masks, residuals)):
+            raise ValueError('one flow (mask, residual) per frame, the first is not used: %d frames, %d flows' % (len(frames), len(flows)))
+        if len(frames) < 2:
+            return self.add_tables(video_id, np.zeros((2, CENSUS_CELLS), dtype=np.int64), 0)
+        for t in range(1, len(frames)):                  # no synchronisation between pairs
+            self.add_pair(frames[t - 1], frames[t], flows[t], mask=None if masks is None else masks[t], residual=None if residuals is None else residuals[t])
+        return self.end_video(video_id)
+
+    def result(self):
+        assert self._n == 0, 'a video opened by add_pair is not ended'
+        return super().result()
+
+
+def write_census_outputs(result, out_dir):
+    """flow-census.txt and flow-census.json in `out_dir`"""
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, 'flow-census.txt'), 'w') as f:
+        f.write(census_text(result))
+    with open(os.path.join(out_dir, 'flow-census.json'), 'w') as f:
         json.dump(result, f, indent=1)

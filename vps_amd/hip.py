@@ -38,6 +38,7 @@ SYMBOLS = [
     'vps_rle_runs', 'vps_rle_runs_ws', 'vps_rle_band_rows', 'vps_rle_strings', 'vps_rle_strings_bound',
     'vps_stq_accumulate', 'vps_stq_lds_cells', 'vps_tc_accumulate', 'vps_tc_accumulate_masked', 'vps_flow_occlusion',
     'vps_flow_error_ws_bytes', 'vps_flow_error', 'vps_flow_photo_ws_bytes', 'vps_flow_photo',
+    'vps_flow_census_ws_bytes', 'vps_flow_census', 'vps_flow_census_tile',
     'vps_boundary_band', 'vps_boundary_band_ws', 'vps_boundary_tile',
     'vps_y4m_info', 'vps_y4m_frame_header', 'vps_y4m_write_header', 'vps_yuv_to_bgr', 'vps_bgr_to_yuv', 'vps_yuv_tile',
 ]
@@ -281,6 +282,11 @@ def load():
     lib.vps_flow_photo_ws_bytes.argtypes = [c_int, c_int]
     lib.vps_flow_photo.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_int64, c_void_p]
+    lib.vps_flow_census_ws_bytes.restype = c_int64                # bytes, or a -100x code
+    lib.vps_flow_census_ws_bytes.argtypes = [c_int, c_int]
+    lib.vps_flow_census.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_int64, c_void_p]
+    lib.vps_flow_census_tile.argtypes = [POINTER(c_int32)]
     lib.vps_boundary_band.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]
     lib.vps_boundary_band_ws.argtypes = [c_int, c_int, c_int, POINTER(c_int64)]
     lib.vps_boundary_tile.argtypes = [POINTER(c_int32)]

@@ -307,11 +307,23 @@ class TcEvaluator(TcStats):
     (`add_pair(.., frames=(prev_bgr, cur_bgr))`, `add_video(.., frames=)`); between the two launches above the pair's mask goes through
     `vps_flow_photo` in place, which turns the visible in-view pixels whose photometric warp error is above THR grey levels into code 3,
     so they are left out of the counts as well: the flow that is wrong but self-consistent in both directions. The tables keep their
-    layout; the masked cell (`occluded`) then holds occluded plus flagged pixels."""
+    layout; the masked cell (`occluded`) then holds occluded plus flagged pixels.
+    census=THR[, census_eps=] (with occlusion=True only): the same with `vps_flow_census` in the place of
+    `vps_flow_photo` - the visible in-view pixels whose ternary census residual is above THR percent become code 3, which brightness
+    changes do not trigger. It takes the two frames of every pair as photometric= does and may be combined with it: the absolute pass
+    runs first, then the census in place."""
 
     def __init__(self, seg_class, num_classes, id_channel=2, device='cuda', per_pair=False, id_last_stuff=None, occlusion=False, alpha=OCC_ALPHA,
-                 beta=OCC_BETA, photometric=None):
+                 beta=OCC_BETA, photometric=None, census=None, census_eps=None):
         super().__init__(seg_class, num_classes)
+        if census is not None and not occlusion:
+            raise ValueError('census= flags pixels in the mask of the occlusion option: it needs occlusion=True')
+        if census is None and census_eps is not None:
+            raise ValueError('census_eps= belongs to census=')
+        self.census = self.census_eps = self._census = None
+        if census is not None:
+            from .flowphoto import CENSUS_EPS, _census_args
+            self.census, self.census_eps = _census_args(census, CENSUS_EPS if census_eps is None else census_eps)
         if photometric is not None and not occlusion:
             raise ValueError('photometric= flags pixels in the mask of the occlusion option: it needs occlusion=True')
         if photometric is not None and not float(photometric) >= 0:
@@ -393,9 +405,10 @@ class TcEvaluator(TcStats):
         these two maps). flicker: None or a device uint8 [H,W] tensor that receives the inconsistency map. back_flow: the flow from
         prev to cur, fp32 [H,W,2] - required by an evaluator with occlusion=True, refused by one without. frames: (prev_bgr, cur_bgr),
         the two frames as uint8 [H,W,3] - required by an evaluator with photometric=, refused by one without. Nothing is downloaded."""
-        if (self.photometric is not None) != (frames is not None):
-            raise ValueError('photometric= needs the two frames of every pair (frames=(prev_bgr, cur_bgr))' if frames is None
-                             else 'frames are given but the evaluator was made without photometric=')
+        census = getattr(self, 'census', None)
+        if (self.photometric is not None or census is not None) != (frames is not None):
+            raise ValueError('photometric= and census= need the two frames of every pair (frames=(prev_bgr, cur_bgr))' if frames is None
+                             else 'frames are given but the evaluator was made without photometric= or census=')
         if self.occlusion != (back_flow is not None):
             raise ValueError('occlusion=True needs the backward flow of every pair (back_flow=)' if self.occlusion
                              else 'back_flow is given but the evaluator was made without occlusion=True')
@@ -433,6 +446,15 @@ class TcEvaluator(TcStats):
                 hip.check(self.lib.vps_flow_photo(hip.ptr(fcur), hip.ptr(fprev), H, W, hip.ptr(flow), ld, 0, hip.ptr(mask), self.photometric,
                                                   hip.ptr(self._photo[0]), hip.ptr(self._photo[1]), hip.ptr(mask), None, hip.ptr(ws), nbytes,
                                                   hip.stream_ptr()), 'vps_flow_photo')
+            if census is not None:                       # in place as well, behind the absolute pass: code 3 for the visible pixels the census flags
+                nbytes = int(self.lib.vps_flow_census_ws_bytes(H, W))
+                hip.check(min(nbytes, 0), 'vps_flow_census_ws_bytes')
+                if self._census is None:                 # a table nobody reads
+                    self._census = torch.zeros(26, dtype=torch.int64, device=self.device)
+                ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+                hip.check(self.lib.vps_flow_census(hip.ptr(fcur), hip.ptr(fprev), H, W, hip.ptr(flow), ld, 0, hip.ptr(mask), census, self.census_eps,
+                                                   hip.ptr(self._census), hip.ptr(mask), None, hip.ptr(ws), nbytes, hip.stream_ptr()),
+                          'vps_flow_census')
             hip.check(self.lib.vps_tc_accumulate_masked(hip.ptr(prev), hip.ptr(cur), H, W, hip.ptr(flow), ld, 0, self.id_channel,
                                                         self.seg_class.ctypes.data_as(ctypes.c_void_p), C, hip.ptr(o['d_keys']) if n else None, n,
                                                         hip.ptr(conf), hip.ptr(psz) if n else None, hip.ptr(csz) if n else None,
@@ -471,8 +493,9 @@ class TcEvaluator(TcStats):
             raise ValueError('one flow per map (the first is not used): %d maps, %d flows' % (len(maps), len(flows)))
         if self.occlusion != (back_flows is not None) or (back_flows is not None and len(back_flows) != len(maps)):
             raise ValueError('occlusion=True takes one backward flow per map (the first is not used), an evaluator without it takes none')
-        if (self.photometric is not None) != (frames is not None) or (frames is not None and len(frames) != len(maps)):
-            raise ValueError('photometric= takes one frame per map, an evaluator without it takes none')
+        if (self.photometric is not None or getattr(self, 'census', None) is not None) != (frames is not None) or \
+                (frames is not None and len(frames) != len(maps)):
+            raise ValueError('photometric= and census= take one frame per map, an evaluator without them takes none')
         maps = [self._map(m) for m in maps]
         self._begin(self.video_keys(maps) if keys is None else keys, max(len(maps) - 1, 0))
         for t in range(1, len(maps)):                    # no synchronisation between pairs
@@ -499,7 +522,7 @@ def score_videos(evaluator, maps, flows, names, nframes_per_video, map_dir=None,
     from .postprocess import DeviceJpegWriter, overlay_name, render_overlay, video_name_of
     assert len(maps) == len(flows) == len(names) and (map_dir is None or (frames is not None and len(frames) == len(maps)))
     assert back_flows is None or len(back_flows) == len(maps)
-    photo = getattr(evaluator, 'photometric', None) is not None
+    photo = getattr(evaluator, 'photometric', None) is not None or getattr(evaluator, 'census', None) is not None
     assert not photo or (frames is not None and len(frames) == len(maps))
     writer = DeviceJpegWriter(evaluator.device, quality=quality, entropy=entropy) if map_dir is not None else None
     out = []
