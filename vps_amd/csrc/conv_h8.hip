@@ -6,6 +6,16 @@
 
 namespace {
 
+// f16x3: derive the third weight plane (2^-11 * plane 0, derive_weight_plane) in registers behind the LDS fragment read, in front
+// of the MFMAs that take it, instead of loading and staging it. Same values and MFMA order either way, bitwise equal results. One
+// switch per kernel, each set from its own rows of profiles/f16x3_plane2_conv_table.txt (ms per frame, all planes loaded -> derived):
+//   h8   (the 3x3 layers run here with VPS_H8P=0): 256->256 3x3 @256x512 2.88 -> 2.78, @128x256 0.667 -> 0.646, 128->128 0.268 -> 0.256
+//   h8s2: 64->128 5x5 s2 @512x1024 0.690 -> 0.665, 128->256 5x5 s2 0.602 -> 0.579, 64->64 3x3 s2 @1024x2048 0.525 -> 0.517,
+//         128->128 3x3 s2 0.278 -> 0.272, 256->512 3x3 s2 @128x256 0.359 -> 0.357
+// (no 2x2 transposed layer of the 1024x2048 frame is planned on h8 in f16x3: that instance is covered by the tests only)
+constexpr bool H8_DERIVE_PLANE2 = true;
+constexpr bool H8S2_DERIVE_PLANE2 = true;
+
 // ================================================================================================
 // Halo-staged, 8 wavefronts, weights shared through LDS ("h8"): the 128-column stride-1 3x3 / 2x2 layers in the 3-product
 // modes (f16x3, bf16x3) and plain bf16, when the layer fills the chip with 256-row tiles.
@@ -33,9 +43,10 @@ void conv_mfma_h8_kernel(const vps_conv_desc d, const int tiles_m, const int til
     constexpr int NSA = SM::NSA, NSB = SM::NSB;
     constexpr int PLANE = NLD * 64 * LDS_LDH;           // 16-bit elements of one plane of one activation buffer
     constexpr int ABUF = NSA * PLANE;
-    // all packed planes are loaded and staged: deriving the f16x3 mode's third plane in registers (derive_weight_plane) saves a third
-    // of the weight traffic but measured slower here (256->256 3x3 @256x512: 2.81 -> 2.88 ms; the tap loop is not short of load slots)
-    constexpr int NLB = NSB;
+    // weight planes loaded and staged. Deriving the plane inside read_B (the wave then waits for the plane-0 fragment in the middle
+    // of the MFMA stream) measured slower in round 6 (256->256 3x3 @256x512: 2.81 -> 2.88 ms); derived in the MFMA loop it gains
+    // (figures at H8_DERIVE_PLANE2)
+    constexpr int NLB = H8_DERIVE_PLANE2 ? SM::NLB : NSB;
     constexpr int NFRAG = NLB * 2 * (BN / 32);          // 1 KB weight fragments of one tap of the block tile
     constexpr int BBUF = NFRAG * 512;
     static_assert((NFRAG * 64) % 512 == 0, "whole 16-byte chunks per thread");
@@ -142,10 +153,6 @@ void conv_mfma_h8_kernel(const vps_conv_desc d, const int tiles_m, const int til
 #pragma unroll
             for (int b = 0; b < TN; ++b)
                 bcur[m][p][b] = *reinterpret_cast<const x8*>(&Bs[buf * BBUF + (((p * 2 + m) * (BN / 32)) + wn * TN + b) * 512 + lane * 8]);
-        if constexpr (NLB < NSB) {
-#pragma unroll
-            for (int b = 0; b < TN; ++b) bcur[m][2][b] = derive_weight_plane<MODE>(bcur[m][0][b]);
-        }
     };
 
     f32x16 acc[TM][TN];
@@ -203,6 +210,10 @@ void conv_mfma_h8_kernel(const vps_conv_desc d, const int tiles_m, const int til
                     for (int a = 0; a < TM; ++a)
 #pragma unroll
                         for (int b = 0; b < TN; ++b) {
+                            if constexpr (NLB < NSB) {
+                                // a plane that is not staged: made from the plane-0 fragment in front of its first MFMA
+                                if (SM::PB[q] >= NLB && a == 0) bcur[m][SM::PB[q]][b] = derive_weight_plane<MODE>(bcur[m][0][b]);
+                            }
                             acc[a][b] = split_mfma<MODE>(bcur[m][SM::PB[q]][b], af[m][SM::PA[q]][a], acc[a][b]);
                             ++mf;
 #pragma unroll
@@ -272,7 +283,7 @@ void conv_mfma_h8s2_kernel(const vps_conv_desc d, const int tiles_m, const int t
     constexpr int NSA = SM::NSA, NSB = SM::NSB;
     constexpr int PLANE = NLD * 64 * LDS_LDH;
     constexpr int ABUF = NSA * PLANE;
-    constexpr int NLB = NSB;                            // all packed planes loaded (see the stride-1 kernel above)
+    constexpr int NLB = H8S2_DERIVE_PLANE2 ? SM::NLB : NSB;   // weight planes loaded and staged (see the stride-1 kernel above)
     constexpr int NFRAG = NLB * 2 * (BN / 32);
     constexpr int NBL = (NFRAG * 64 + 511) / 512;       // 16-byte weight chunks per thread
     constexpr bool WHOLE = (NFRAG * 64) % 512 == 0;
@@ -377,10 +388,6 @@ void conv_mfma_h8s2_kernel(const vps_conv_desc d, const int tiles_m, const int t
 #pragma unroll
             for (int b = 0; b < TN; ++b)
                 bcur[m][p][b] = *reinterpret_cast<const x8*>(&Bs[buf * BBUF + (((p * 2 + m) * (BN / 32)) + wn * TN + b) * 512 + lane * 8]);
-        if constexpr (NLB < NSB) {
-#pragma unroll
-            for (int b = 0; b < TN; ++b) bcur[m][2][b] = derive_weight_plane<MODE>(bcur[m][0][b]);
-        }
     };
 
     f32x16 acc[TM][TN];
@@ -440,6 +447,10 @@ void conv_mfma_h8s2_kernel(const vps_conv_desc d, const int tiles_m, const int t
                     for (int a = 0; a < TM; ++a)
 #pragma unroll
                         for (int b = 0; b < TN; ++b) {
+                            if constexpr (NLB < NSB) {
+                                // a plane that is not staged: made from the plane-0 fragment in front of its first MFMA
+                                if (SM::PB[q] >= NLB && a == 0) bcur[m][SM::PB[q]][b] = derive_weight_plane<MODE>(bcur[m][0][b]);
+                            }
                             acc[a][b] = split_mfma<MODE>(bcur[m][SM::PB[q]][b], af[m][SM::PA[q]][a], acc[a][b]);
                             ++mf;
 #pragma unroll

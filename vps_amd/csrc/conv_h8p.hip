@@ -9,7 +9,10 @@
 // Here:
 //   * weights: requested THREE taps ahead into one of three register sets (index = tap % 3, static in the unrolled tap loop: 9 % 3 = 0),
 //     staged two taps ahead into a ring of three LDS slots; only the two packed planes are loaded, the f16x3 mode's third plane
-//     (2^-11 * plane 0) is made by the staging thread (a third less weight traffic through the vector-memory pipe);
+//     (2^-11 * plane 0, derive_weight_plane) is made by every wave from the plane-0 fragment it has read from LDS, right in front of
+//     the MFMAs that take it: a third less weight traffic through the vector-memory pipe AND through LDS (stores and fragment
+//     reads), for 4 packed fp16 multiplies per fragment and wave. Until the plane was derived by the staging thread and went through
+//     the ring like the loaded ones; per-layer table profiles/f16x3_plane2_conv_table.txt: 256->256 3x3 @256x512 2.82 -> 2.73 ms;
 //   * activations: the rows of chunk c+1 are staged in the FIRST half of chunk c's taps, the loads of chunk c+2 go out right behind
 //     them - half a chunk (4-5 taps) of flight instead of half a tap;
 //   * fragments: always one 16-k slab ahead of the MFMAs that use them, ACROSS the barrier - the second slab of a tap is read under
@@ -17,7 +20,7 @@
 //     tap before, its activations in the chunk buffer); reads and MFMAs alternate one to one in program order.
 // Accumulation order per output element is conv_mfma_h8_kernel's: results are bitwise equal (tests/test_hip_ops.py).
 // LDS: activations 2 buffers x 2 planes x 340 rows x 64 B = 85 KB (rows beyond the halo tile are not kept any more), weights 3 slots x
-// 24 KB = 72 KB: 157 KB of the CU's 160.
+// 2 planes x 8 KB = 48 KB: 133 KB of the CU's 160.
 #include "conv_common.h"
 
 namespace {
@@ -46,9 +49,9 @@ void conv_mfma_h8p_kernel(const vps_conv_desc d, const int tiles_m, const int ti
     constexpr int NSA = SM::NSA, NSB = SM::NSB, NLB = SM::NLB, NT = SM::NT;
     constexpr int PLANE = HROWS * LDS_LDH;              // 16-bit elements of one plane of one activation buffer
     constexpr int ABUF = NSA * PLANE;
-    constexpr int NFRAG = NSB * 2 * (BN / 32);          // 1 KB weight fragments of one tap of the block tile, all planes
+    constexpr int NFRAG = NLB * 2 * (BN / 32);          // 1 KB weight fragments of one tap of the block tile, the loaded planes
     constexpr int BBUF = NFRAG * 512;
-    static_assert(NFRAG * 64 == NSB * 512, "thread t stages chunk t of every plane");
+    static_assert(NFRAG * 64 == NLB * 512, "thread t stages chunk t of every loaded plane");
     static_assert((2 * ABUF + 3 * BBUF) * 2 <= 160 * 1024, "LDS budget of the CU");
 
     __shared__ __attribute__((aligned(16))) elem_t As[2 * ABUF];
@@ -129,7 +132,6 @@ void conv_mfma_h8p_kernel(const vps_conv_desc d, const int tiles_m, const int ti
     auto store_B = [&](const int slot, const int set) {
 #pragma unroll
         for (int p = 0; p < NLB; ++p) *reinterpret_cast<x8*>(&Bs[slot * BBUF + (t + 512 * p) * 8]) = breg[set][p];
-        if constexpr (NLB < NSB) *reinterpret_cast<x8*>(&Bs[slot * BBUF + (t + 512 * NLB) * 8]) = derive_weight_plane<MODE>(breg[set][0]);
     };
 
     // halo row of tile row j = wm*64 + a*32 + (lane&31) = patch row 2 wm + a, column lane&31, for tap (0,0); tap (ky,kx) adds ky*HW + kx
@@ -139,7 +141,7 @@ void conv_mfma_h8p_kernel(const vps_conv_desc d, const int tiles_m, const int ti
     x8 af[2][NSA][TM];
     x8 bcur[2][NSB][TN];
     // fragment reads, ONE at a time (they are dealt out between the MFMAs): index j < NRD of slab m
-    constexpr int NRD = NSA * TM + NSB * TN;
+    constexpr int NRD = NSA * TM + NLB * TN;
     auto read_frag = [&](const int j, const int m, const int abuf, const int toff, const int slot) {
         if (j < NSA * TM) {
             const int p = j / TM, a = j - p * TM;
@@ -179,6 +181,10 @@ void conv_mfma_h8p_kernel(const vps_conv_desc d, const int tiles_m, const int ti
     constexpr int SPT = (NLD + STG - 1) / STG;                  // rows staged per tap
     auto mfma = [&](const int m, const int i) {
         const int q = i / (TM * TN), r = i - q * (TM * TN), a = r / TN, b = r - a * TN;
+        if constexpr (NLB < NSB) {
+            // a plane that is not loaded: made from the plane-0 fragment (read a slab ago) in front of its first MFMA
+            if (SM::PB[q] >= NLB && a == 0) bcur[m][SM::PB[q]][b] = derive_weight_plane<MODE>(bcur[m][0][b]);
+        }
         acc[a][b] = split_mfma<MODE>(bcur[m][SM::PB[q]][b], af[m][SM::PA[q]][a], acc[a][b]);
     };
 
