@@ -392,6 +392,43 @@ int vps_png_reconstruct(const uint8_t* scan, int H, int W, int channels, uint8_t
                         void* ws, int64_t ws_bytes, void* stream);
 int vps_png_reconstruct_block_rows(void);
 
+/* KITTI flow files (csrc/png_host.cpp, csrc/png_in_ops.hip, csrc/kitti_flow_ops.hip; vps_amd/kittiflow.py): optical
+ * flow as a 16-bit RGB PNG. The coding is restated from memory of the KITTI devkit's io_flow.h; tests/kitti_flow_restate.py pins it.
+ *   file    non-interlaced PNG, colour type 2, bit depth 16; samples big-endian in the order R, G, B: 6 bytes per pixel
+ *   read    a pixel is valid iff B > 0 (the 16-bit value); then u = (R - 32768) / 64, v = (G - 32768) / 64, exact in fp32; an invalid
+ *           pixel reads as u = v = 0
+ *   write   R = (uint16) max(min(u * 64.0f + 32768.0f, 65535.0f), 0.0f) in fp32, the cast truncating behind the clamp; G likewise from
+ *           v; B = 1 where valid, 0 otherwise. This library's own rule: a pixel whose u or v is NaN or +-inf is written R = G = B = 0
+ * vps_png16_info, vps_png16_inflate (HOST, no device work, no stream, no interpreter lock, no allocation): vps_png_info / vps_png_inflate
+ * for exactly this flavour - depth 16, colour type 2, not interlaced; every other file is refused with their codes (-1001 signature,
+ * IHDR or its CRC, -1002 size, -1003 flavour, -1004 scan NULL or scan_capacity too small, -1007 stream incomplete or a chunk cut,
+ * -1008 a filter byte above 4, -1009 more than 1 GiB of scanlines), and the IEND chunk must be there (-1007). channels = 3. scan
+ * receives H rows of 1 + 6 W bytes; nothing is written behind scan_capacity. vps_png_info keeps refusing these files.
+ * vps_kitti_flow_reconstruct_ws (HOST arithmetic only): the workspace bytes of vps_kitti_flow_reconstruct.
+ * vps_kitti_flow_reconstruct: every pointer is a DEVICE pointer; two launches on `stream`, no sync, no allocation. Un-filters the scan
+ * at 6 bytes per pixel with vps_png_reconstruct's wavefront (one lane per row, groups cut by None / Sub rows, bands of
+ * vps_png_reconstruct_block_rows() rows) and decodes in the same launch.
+ *   scan        as vps_png16_inflate wrote it, at any byte address; read as aligned dwords (up to 3 bytes in front of and behind it
+ *               are loaded and ignored, as vps_png_reconstruct)
+ *   noc_valid   NULL, or uint8 [H][W], any byte alignment: non-zero = the pixel is valid in the pair's flow_noc file
+ *   flow        fp32 [H][W][2] dense, 16-byte aligned; flow_capacity in BYTES >= 8 H W
+ *   mask        uint8 [H][W], any byte alignment, in vps_flow_error's codes. noc_valid NULL: 1 valid, 0 invalid. noc_valid given: 1 valid
+ *               here and in noc, 2 valid here but not in noc (occluded), 0 invalid here
+ *   ws          4-byte aligned, at least vps_kitti_flow_reconstruct_ws bytes: the group table and, for every band that another follows,
+ *               its last rebuilt raw row (the decoded flow no longer holds B, so the next band cannot read it back from the output)
+ * Errors before any launch: -1001 a null pointer or H, W outside 1..65535, -1003 ws or flow misaligned, -1004 flow_capacity,
+ * -1006 ws_bytes.
+ * vps_kitti_flow_encode: flow = DEVICE fp32 NHWC map in any layout vps_flow_colour takes (pixel p at flow[p * ld + coff] (u) and
+ * [.. + 1] (v), coff + 2 <= ld, 4-byte aligned); valid = NULL (every pixel valid) or DEVICE uint8 [H][W]; img16 = DEVICE uint8
+ * [H][6 W], dense, 4-byte aligned: the big-endian RGB16 image by the write rule. One launch on `stream`, no sync, no allocation. Errors
+ * before the launch: -1001 flow or img16 NULL, -1002 H, W outside 1..65535, -1003 ld / coff, -1004 alignment. */
+int vps_png16_info(const uint8_t* file, int64_t nbytes, int32_t* H, int32_t* W, int32_t* channels);
+int vps_png16_inflate(const uint8_t* file, int64_t nbytes, uint8_t* scan, int64_t scan_capacity);
+int vps_kitti_flow_reconstruct_ws(int H, int W, int64_t* ws_bytes);
+int vps_kitti_flow_reconstruct(const uint8_t* scan, int H, int W, const uint8_t* noc_valid, float* flow, int64_t flow_capacity,
+                               uint8_t* mask, void* ws, int64_t ws_bytes, void* stream);
+int vps_kitti_flow_encode(const float* flow, int ld, int coff, const uint8_t* valid, int H, int W, uint8_t* img16, void* stream);
+
 /* JPEG input (the VIPER frames). The Huffman bit stream is decoded on the HOST (two functions, no device work, no stream, no
  * interpreter lock, no allocation); dequantisation, the 8x8 inverse DCT, chroma upsampling and YCbCr -> BGR run on the DEVICE and are
  * bit-exact with libjpeg's default decode (slow-integer IDCT, fancy upsampling, 16-bit fixed-point colour) - what cv2.imread and PIL
@@ -888,6 +925,14 @@ int vps_boundary_tile(int32_t* rows_cols);
 int vps_png_encode_bound(int H, int W, int channels, int64_t* out_capacity, int64_t* ws_bytes);
 int vps_png_deflate(const uint8_t* img, int H, int W, int channels, int64_t row_stride, uint8_t* out, int64_t out_capacity,
                     int64_t* out_nbytes, void* ws, int64_t ws_bytes, void* stream);
+/* The same chain for a row given in bytes and a pixel of bpp bytes: H rows of rowbytes bytes (a multiple of bpp, at most 65535 pixels),
+ * bpp = 1 (grey), 3 (RGB) or 6 (RGB with 16-bit samples, the KITTI flow files). S = the rows in order, each its filter byte + rowbytes
+ * residuals, N = H * (1 + rowbytes); Sub takes the byte bpp to the left; filter choice, segments, bits and stream are the ones above,
+ * and for bpp 1 / 3 the bytes are vps_png_deflate's. -1002 for another bpp, -1001 for a bad H or rowbytes; the other codes, pointers,
+ * alignments and out_nbytes as vps_png_deflate. */
+int vps_png_encode_bound_bpp(int H, int64_t rowbytes, int bpp, int64_t* out_capacity, int64_t* ws_bytes);
+int vps_png_deflate_bpp(const uint8_t* img, int H, int64_t rowbytes, int bpp, int64_t row_stride, uint8_t* out, int64_t out_capacity,
+                        int64_t* out_nbytes, void* ws, int64_t ws_bytes, void* stream);
 
 /* Optical-flow output (csrc/flow_vis_ops.hip; vps_amd/flowvis.py): the colour coding of the reference's flow_utils.py (vis_flow) on the
  * device. Both launch on `stream`, no sync, no hidden allocation. flow: DEVICE fp32 NHWC map of H x W pixels, pixel p at

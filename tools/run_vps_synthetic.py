@@ -328,7 +328,7 @@ def parse_args(argv=None):
                     help='where the JPEG files of --overlay and --flow are Huffman-coded; the files are the same (default host)')
     ap.add_argument('--tubes', action='store_true', help='write pred/tubes.json: run-length encoded masks, boxes and areas of every tracked instance (off by default)')
     ap.add_argument('--flow', default=None, metavar='DIR', help='write DIR/<name>.<ext> for every frame: the FlowNet2 flow of the frame (off by default)')
-    ap.add_argument('--flow-format', default='jpg', choices=['jpg', 'png', 'flo'], help='colour image (jpg, png) or the raw Middlebury field (flo)')
+    ap.add_argument('--flow-format', default='jpg', choices=['jpg', 'png', 'flo', 'kitti'], help="colour image (jpg, png), the raw Middlebury field (flo) or the KITTI devkit's 16-bit PNG (kitti)")
     ap.add_argument('--flow-max-rad', type=float, default=None, metavar='X', help='one normaliser of the flow colours for all frames (default: each frame its own maximum)')
     ap.add_argument('--stq', action='store_true', help='after the VPQ step, score the same files with tools/eval_stq_device.py: pred/stq.txt and '
                     'pred/stq-tracks.json (off by default)')

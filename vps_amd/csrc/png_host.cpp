@@ -7,6 +7,9 @@
 // falls back to its general decoder. Output: BGR uint8 [H][W][3] (cv2 / mmcv channel order). zlib does the inflate.
 // vps_png_inflate is the host half of the opt-in split (`ClipFeeder(png='device')`): the same files, checks and error codes, but the
 // filtered scanlines are left as zlib delivers them, in the caller's buffer, for vps_png_reconstruct (png_in_ops.hip) to un-filter.
+// vps_png16_info / vps_png16_inflate are the same two steps for ONE more flavour, 16-bit RGB (the KITTI flow files, vps_amd/kittiflow.py;
+// un-filter and decode: vps_kitti_flow_reconstruct): they share the header check, the chunk walk and the inflate; the 8-bit entry points
+// keep refusing that flavour.
 #include <zlib.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -83,18 +86,45 @@ inline void unfilter_sub(uint8_t* cur, size_t stride) {
 
 }  // namespace
 
-extern "C" int vps_png_info(const uint8_t* file, int64_t nbytes, int32_t* H, int32_t* W, int32_t* channels) {
+namespace {
+
+// what vps_png_info and vps_png16_info share: signature, the IHDR chunk with its CRC, the size limit. The flavour (depth, colour type,
+// interlace) is left to the caller: each entry point takes its own and refuses the rest with VPS_EARG(3).
+struct PngHeader { uint32_t w, h; int depth, ctype, interlace; };
+
+inline int png_header(const uint8_t* file, int64_t nbytes, PngHeader* hd) {
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
     if (!file || nbytes < 33 || memcmp(file, sig, 8) != 0 || be32(file + 8) != 13 || memcmp(file + 12, "IHDR", 4) != 0) return VPS_EARG(1);
     // the IHDR chunk's CRC (type + 13 data bytes): a damaged header is refused before its fields size anything
     if ((uint32_t)crc32(0L, file + 12, 17) != be32(file + 29)) return VPS_EARG(1);
-    const uint32_t w = be32(file + 16), h = be32(file + 20);
-    const int depth = file[24], ctype = file[25], interlace = file[28];
-    if (w == 0 || h == 0 || w > 65535 || h > 65535) return VPS_EARG(2);
-    if (depth != 8 || interlace != 0 || !(ctype == 0 || ctype == 2 || ctype == 6)) return VPS_EARG(3);      // caller falls back
-    if (H) *H = (int32_t)h;
-    if (W) *W = (int32_t)w;
-    if (channels) *channels = ctype == 0 ? 1 : (ctype == 2 ? 3 : 4);
+    hd->w = be32(file + 16); hd->h = be32(file + 20);
+    hd->depth = file[24]; hd->ctype = file[25]; hd->interlace = file[28];
+    if (hd->w == 0 || hd->h == 0 || hd->w > 65535 || hd->h > 65535) return VPS_EARG(2);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int vps_png_info(const uint8_t* file, int64_t nbytes, int32_t* H, int32_t* W, int32_t* channels) {
+    PngHeader hd;
+    const int st = png_header(file, nbytes, &hd);
+    if (st) return st;
+    if (hd.depth != 8 || hd.interlace != 0 || !(hd.ctype == 0 || hd.ctype == 2 || hd.ctype == 6)) return VPS_EARG(3);      // caller falls back
+    if (H) *H = (int32_t)hd.h;
+    if (W) *W = (int32_t)hd.w;
+    if (channels) *channels = hd.ctype == 0 ? 1 : (hd.ctype == 2 ? 3 : 4);
+    return 0;
+}
+
+// the 16-bit RGB flavour (KITTI's flow files): nothing else passes, and vps_png_info keeps refusing this one
+extern "C" int vps_png16_info(const uint8_t* file, int64_t nbytes, int32_t* H, int32_t* W, int32_t* channels) {
+    PngHeader hd;
+    const int st = png_header(file, nbytes, &hd);
+    if (st) return st;
+    if (hd.depth != 16 || hd.interlace != 0 || hd.ctype != 2) return VPS_EARG(3);
+    if (H) *H = (int32_t)hd.h;
+    if (W) *W = (int32_t)hd.w;
+    if (channels) *channels = 3;
     return 0;
 }
 
@@ -102,14 +132,16 @@ namespace {
 
 // what vps_png_decode_bgr8 and vps_png_inflate share: header, the size limit, the chunk walk and the inflate of the IDAT data into `raw`
 // (`need(total)` names the buffer once the header has sized it: the thread's scratch, or the caller's). On success raw holds H rows of
-// 1 + W*C bytes, each led by its filter byte, still filtered.
+// 1 + W*C*B bytes, each led by its filter byte, still filtered. B = bytes per sample: 1 through vps_png_info, 2 through vps_png16_info,
+// which also asks for the IEND chunk (`need_iend`: a ground-truth file cut behind its last IDAT is refused; the 8-bit path keeps taking it).
 struct PngGeom { int32_t H, W, C; size_t stride; };
 
 template <class Need>
-int inflate_idat(const uint8_t* file, int64_t nbytes, PngGeom* g, uint8_t** raw_out, Need need) {
-    const int st = vps_png_info(file, nbytes, &g->H, &g->W, &g->C);
+int inflate_idat(const uint8_t* file, int64_t nbytes, PngGeom* g, uint8_t** raw_out, Need need, bool wide = false) {
+    const int st = wide ? vps_png16_info(file, nbytes, &g->H, &g->W, &g->C) : vps_png_info(file, nbytes, &g->H, &g->W, &g->C);
     if (st) return st;
-    g->stride = (size_t)g->W * g->C;
+    g->stride = (size_t)g->W * g->C * (wide ? 2 : 1);
+    const bool need_iend = wide;
     const size_t total = (g->stride + 1) * (size_t)g->H;                  // filter byte + pixels per scanline
     uint8_t* raw = nullptr;
     const int sn = need(*g, total, &raw);
@@ -136,7 +168,7 @@ int inflate_idat(const uint8_t* file, int64_t nbytes, PngGeom* g, uint8_t** raw_
         }
         pos += 12 + (int64_t)len;
     }
-    const bool complete = zs.avail_out == 0 && (zret == Z_STREAM_END || zret == Z_OK);
+    const bool complete = zs.avail_out == 0 && (zret == Z_STREAM_END || zret == Z_OK) && (end || !need_iend);
     inflateEnd(&zs);
     if (!complete) return VPS_EARG(7);
     *raw_out = raw;
@@ -150,20 +182,33 @@ inline bool too_large(size_t total) { return total > ((size_t)1 << 30); }
 
 }  // namespace
 
-extern "C" int vps_png_inflate(const uint8_t* file, int64_t nbytes, uint8_t* scan, int64_t scan_capacity) {
+namespace {
+
+// vps_png_inflate and vps_png16_inflate: straight into the caller's (pinned) buffer, then every filter byte checked
+inline int inflate_to_scan(const uint8_t* file, int64_t nbytes, uint8_t* scan, int64_t scan_capacity, bool wide) {
     PngGeom g;
     uint8_t* raw = nullptr;
     const int st = inflate_idat(file, nbytes, &g, &raw, [&](const PngGeom&, size_t total, uint8_t** p) {
         if (!scan || scan_capacity < 0 || (uint64_t)scan_capacity < total) return VPS_EARG(4);
         if (too_large(total)) return VPS_EARG(9);
-        *p = scan;                                                       // straight into the caller's (pinned) buffer
+        *p = scan;
         return 0;
-    });
+    }, wide);
     if (st) return st;
     // the device stage never sees a filter type outside 0..4
     for (int y = 0; y < g.H; ++y)
         if (raw[(size_t)y * (g.stride + 1)] > 4) return VPS_EARG(8);
     return 0;
+}
+
+}  // namespace
+
+extern "C" int vps_png_inflate(const uint8_t* file, int64_t nbytes, uint8_t* scan, int64_t scan_capacity) {
+    return inflate_to_scan(file, nbytes, scan, scan_capacity, false);
+}
+
+extern "C" int vps_png16_inflate(const uint8_t* file, int64_t nbytes, uint8_t* scan, int64_t scan_capacity) {
+    return inflate_to_scan(file, nbytes, scan, scan_capacity, true);
 }
 
 extern "C" int vps_png_decode_bgr8(const uint8_t* file, int64_t nbytes, uint8_t* out, int64_t out_capacity) {

@@ -72,7 +72,12 @@ void png_filter_kernel(const uint8_t* __restrict__ img, int rowbytes, int C, int
             cur = *reinterpret_cast<const uint32_t*>(row + x0);
             if (up) above = *reinterpret_cast<const uint32_t*>(up + x0);
             const uint32_t before = x0 ? *reinterpret_cast<const uint32_t*>(row + x0 - 4) : 0u;
-            left = (uint32_t)(((((uint64_t)cur) << 32) | before) >> (8 * (4 - C)));
+            if (C <= 4) {
+                left = (uint32_t)(((((uint64_t)cur) << 32) | before) >> (8 * (4 - C)));
+            } else {                                             // C in 5 .. 8 (16-bit RGB: 6): the bytes to the left lie in the two words before
+                const uint32_t before2 = x0 >= 8 ? *reinterpret_cast<const uint32_t*>(row + x0 - 8) : 0u;
+                left = (uint32_t)(((((uint64_t)before) << 32) | before2) >> (8 * (8 - C)));
+            }
         } else {
             cur = 0; left = 0;
             for (int k = 0; k < 4; ++k) {
@@ -406,12 +411,17 @@ static int png_geometry(int H, int W, int channels, int64_t& rowlen, int64_t& N,
     return 0;
 }
 
-}  // namespace
+// the same for a row given in bytes and a pixel of bpp bytes (1 grey, 3 RGB, 6 RGB with 16-bit samples): Sub reaches back bpp bytes
+static int png_geometry_bpp(int H, int64_t rowbytes, int bpp, int64_t& rowlen, int64_t& N, int64_t& nseg) {
+    if (bpp != 1 && bpp != 3 && bpp != 6) return VPS_EARG(2);
+    if (H <= 0 || H > 65535 || rowbytes <= 0 || rowbytes > (int64_t)65535 * bpp || rowbytes % bpp != 0) return VPS_EARG(1);
+    rowlen = 1 + rowbytes;
+    N = (int64_t)H * rowlen;
+    nseg = (N + PNG_SEG - 1) / PNG_SEG;
+    return 0;
+}
 
-extern "C" int vps_png_encode_bound(int H, int W, int channels, int64_t* out_capacity, int64_t* ws_bytes) {
-    int64_t rowlen, N, nseg;
-    const int rc = png_geometry(H, W, channels, rowlen, N, nseg);
-    if (rc) return rc;
+static int png_bound(int H, int64_t N, int64_t nseg, int64_t* out_capacity, int64_t* ws_bytes) {
     if (!out_capacity || !ws_bytes) return VPS_EARG(3);
     const int64_t last = N - (nseg - 1) * PNG_SEG;
     *out_capacity = 2 + (nseg - 1) * (int64_t)PNG_SEG_MAX + ((9 * last + 7) / 8 + 7) + 6;
@@ -419,12 +429,45 @@ extern "C" int vps_png_encode_bound(int H, int W, int channels, int64_t* out_cap
     return 0;
 }
 
-extern "C" int vps_png_deflate(const uint8_t* img, int H, int W, int channels, int64_t row_stride, uint8_t* out, int64_t out_capacity,
-                               int64_t* out_nbytes, void* ws, int64_t ws_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+static int png_deflate_launch(const uint8_t* img, int H, int bpp, int64_t rowlen, int64_t N, int64_t nseg, int64_t row_stride, uint8_t* out,
+                              int64_t out_capacity, int64_t* out_nbytes, void* ws, int64_t ws_bytes, hipStream_t stream);
+
+}  // namespace
+
+extern "C" int vps_png_encode_bound(int H, int W, int channels, int64_t* out_capacity, int64_t* ws_bytes) {
     int64_t rowlen, N, nseg;
     const int rc = png_geometry(H, W, channels, rowlen, N, nseg);
     if (rc) return rc;
+    return png_bound(H, N, nseg, out_capacity, ws_bytes);
+}
+
+extern "C" int vps_png_encode_bound_bpp(int H, int64_t rowbytes, int bpp, int64_t* out_capacity, int64_t* ws_bytes) {
+    int64_t rowlen, N, nseg;
+    const int rc = png_geometry_bpp(H, rowbytes, bpp, rowlen, N, nseg);
+    if (rc) return rc;
+    return png_bound(H, N, nseg, out_capacity, ws_bytes);
+}
+
+extern "C" int vps_png_deflate(const uint8_t* img, int H, int W, int channels, int64_t row_stride, uint8_t* out, int64_t out_capacity,
+                               int64_t* out_nbytes, void* ws, int64_t ws_bytes, void* stream_) {
+    int64_t rowlen, N, nseg;
+    const int rc = png_geometry(H, W, channels, rowlen, N, nseg);
+    if (rc) return rc;
+    return png_deflate_launch(img, H, channels, rowlen, N, nseg, row_stride, out, out_capacity, out_nbytes, ws, ws_bytes, (hipStream_t)stream_);
+}
+
+extern "C" int vps_png_deflate_bpp(const uint8_t* img, int H, int64_t rowbytes, int bpp, int64_t row_stride, uint8_t* out, int64_t out_capacity,
+                                   int64_t* out_nbytes, void* ws, int64_t ws_bytes, void* stream_) {
+    int64_t rowlen, N, nseg;
+    const int rc = png_geometry_bpp(H, rowbytes, bpp, rowlen, N, nseg);
+    if (rc) return rc;
+    return png_deflate_launch(img, H, bpp, rowlen, N, nseg, row_stride, out, out_capacity, out_nbytes, ws, ws_bytes, (hipStream_t)stream_);
+}
+
+namespace {
+
+static int png_deflate_launch(const uint8_t* img, int H, int channels, int64_t rowlen, int64_t N, int64_t nseg, int64_t row_stride, uint8_t* out,
+                              int64_t out_capacity, int64_t* out_nbytes, void* ws, int64_t ws_bytes, hipStream_t stream) {
     if (!img || !out || !out_nbytes || !ws) return VPS_EARG(3);
     if (row_stride < rowlen - 1 || out_capacity < 0) return VPS_EARG(4);
     if (((uintptr_t)ws & 15) || ((uintptr_t)out_nbytes & 7)) return VPS_EARG(5);
@@ -441,3 +484,5 @@ extern "C" int vps_png_deflate(const uint8_t* img, int H, int W, int channels, i
                        (const int64_t*)w.offset, (const int32_t*)w.ok, (const uint8_t*)w.slots, out);
     return vps_launch_status();
 }
+
+}  // namespace

@@ -31,7 +31,7 @@ With `occ_pred`, over the valid pixels (n + bad), "predicted occluded" = code 1 
 mask value 2:
     occ_precision = TP / (TP + FP), occ_recall = TP / (TP + FN), occ_f1 = 2 P R / (P + R),
     occ_pred_share = (TP + FP) / valid, occ_true_share = occ pixels / valid
-Out of scope: KITTI's 16-bit PNG ground truth (the host PNG decoder is 8-bit only), angular error, and running FlowNet2 on frames whose
+KITTI's 16-bit PNG ground truth is read by vps_amd/kittiflow.py. Out of scope: angular error, and running FlowNet2 on frames whose
 size is no multiple of 64 (a 436 x 1024 Sintel frame needs padding that `FlowNet2.run` does not do for general sizes).
 
 `flow_from_tables`, `FlowEvalStats` and `flow_text` are NumPy / Python only. The counting (`flow_error`, `FlowEvaluator`) is

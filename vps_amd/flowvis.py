@@ -17,7 +17,7 @@ from . import hip, nhwc
 from . import postprocess as pp
 
 FLO_TAG = 202021.25                    # 'PIEH' read as a little-endian float32
-FORMATS = ('jpg', 'png', 'flo')
+FORMATS = ('jpg', 'png', 'flo', 'kitti')
 
 
 def _flow_view(flow):
@@ -140,6 +140,8 @@ class FlowWriter:
                  ('host' or 'device') is that writer's: where the Huffman coding runs, the files are the same
       fmt 'png'  `flow_colour` into a fresh image, handed to a `DevicePngWriter` of its own
       fmt 'flo'  a stream-ordered copy of the two channels into one of `slots` pinned slots; a worker writes header + field
+      fmt 'kitti' the KITTI devkit's 16-bit PNG (vps_amd/kittiflow.py), every pixel valid: `kitti_flow_encode` + `png_deflate_bpp` into one
+                 of `slots` ring slots on the current stream; a worker copies the stream on its own copy stream and writes the file
     max_rad (jpg / png): None = each frame's own maximum (the reference); a float or device float64 scalar = one normaliser for all
     frames. Counters: `submitted`; after `close()`, which joins and re-raises a worker's exception: `written`, `bytes_written`."""
 
@@ -156,12 +158,14 @@ class FlowWriter:
             self.images = pp.DevicePngWriter(self.device, workers=workers, slots=slots)
         else:
             import queue
+            import threading
             from concurrent.futures import ThreadPoolExecutor
             self.pool = ThreadPoolExecutor(max_workers=workers)
             self.futures = []
             self.free = queue.Queue()
+            self.local = threading.local()
             for _ in range(slots):
-                self.free.put(_FloSlot())
+                self.free.put(_FloSlot() if fmt == 'flo' else pp._PngSlot(self.device))
         self.submitted = 0
         self.written = 0
         self.bytes_written = 0
@@ -177,10 +181,49 @@ class FlowWriter:
             self.free.put(slot)
         return name
 
+    def _finish_kitti(self, slot, name, H, W):
+        from . import kittiflow
+        try:
+            slot.event.synchronize()                     # the worker waits, not the caller
+            n = int(slot.size_host[0])
+            if n < 0:
+                raise hip.VpsHipError('vps_png_deflate_bpp: the stream did not fit its worst-case bound')
+            if not hasattr(self.local, 'stream'):
+                self.local.stream = torch.cuda.Stream(self.device)
+            with torch.cuda.stream(self.local.stream):
+                host = slot.staging(n)
+                host.copy_(slot.out[:n], non_blocking=True)
+                self.local.stream.synchronize()
+                data = kittiflow.png16_container(host.numpy().tobytes(), H, W)
+        finally:
+            slot.image = None
+            self.free.put(slot)
+        os.makedirs(os.path.dirname(name) or '.', exist_ok=True)
+        with open(name, 'wb') as f:
+            f.write(data)
+        return name
+
+    def _submit_kitti(self, flow, name, H, W):
+        from . import kittiflow
+        slot = self.free.get()                           # blocks only when every slot is in flight
+        try:
+            slot.fit(*kittiflow.png_encode_bound_bpp(H, 6 * W, 6))
+            slot.image = kittiflow.kitti_flow_encode(flow)               # reads the flow on the current stream; alive until the worker is done
+            kittiflow.png_deflate_bpp(slot.image, 6, slot.out, slot.ws, slot.size)
+            slot.size_host.copy_(slot.size, non_blocking=True)
+            slot.event.record()
+        except BaseException:
+            slot.image = None
+            self.free.put(slot)
+            raise
+        self.futures.append(self.pool.submit(self._finish_kitti, slot, name, H, W))
+
     def submit(self, flow, name):
         view = _flow_view(flow)
         t, ld, coff, H, W = view
-        if self.fmt != 'flo':
+        if self.fmt == 'kitti':
+            self._submit_kitti(flow, name, H, W)
+        elif self.fmt != 'flo':
             rgb = torch.empty(H, W, 3, dtype=torch.uint8, device=t.device)
             rad = _max_radius(view) if self.max_rad is None else self.max_rad
             hip.check(hip.load().vps_flow_colour(hip.ptr(t), ld, coff, H, W, hip.ptr(rad), hip.ptr(rgb), hip.stream_ptr()), 'vps_flow_colour')
@@ -212,8 +255,8 @@ class FlowWriter:
 
 
 def flow_name(save_folder, name, fmt='jpg'):
-    """output file of the flow of an input image name: DIR/<name without its extension>.<fmt>"""
-    return os.path.join(save_folder, os.path.splitext(os.path.basename(name))[0] + '.' + fmt)
+    """output file of the flow of an input image name: DIR/<name without its extension>.<fmt>; a KITTI flow file is a .png"""
+    return os.path.join(save_folder, os.path.splitext(os.path.basename(name))[0] + '.' + ('png' if fmt == 'kitti' else fmt))
 
 
 def write_flows(flows, names, out_dir, device='cuda', fmt='jpg', quality=90, max_rad=None, writer=None, entropy='host'):

@@ -41,6 +41,8 @@ SYMBOLS = [
     'vps_flow_census_ws_bytes', 'vps_flow_census', 'vps_flow_census_tile',
     'vps_boundary_band', 'vps_boundary_band_ws', 'vps_boundary_tile',
     'vps_y4m_info', 'vps_y4m_frame_header', 'vps_y4m_write_header', 'vps_yuv_to_bgr', 'vps_bgr_to_yuv', 'vps_yuv_tile',
+    'vps_png16_info', 'vps_png16_inflate', 'vps_kitti_flow_reconstruct_ws', 'vps_kitti_flow_reconstruct', 'vps_kitti_flow_encode',
+    'vps_png_encode_bound_bpp', 'vps_png_deflate_bpp',
 ]
 
 
@@ -205,6 +207,9 @@ def load():
         h.vps_png_decode_bgr8.argtypes = [c_void_p, c_int64, c_void_p, c_int64]
         h.vps_png_inflate.restype = c_int
         h.vps_png_inflate.argtypes = [c_void_p, c_int64, c_void_p, c_int64]
+        h.vps_png16_info.restype = h.vps_png16_inflate.restype = c_int
+        h.vps_png16_info.argtypes = h.vps_png_info.argtypes
+        h.vps_png16_inflate.argtypes = h.vps_png_inflate.argtypes
         h.vps_jpeg_info.restype = h.vps_jpeg_decode_coef.restype = c_int
         h.vps_jpeg_info.argtypes = [c_void_p, c_int64, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
                                     c_void_p, POINTER(c_int64)]
@@ -244,6 +249,11 @@ def load():
     lib.vps_png_reconstruct_block_rows.argtypes = []
     lib.vps_png_encode_bound.argtypes = [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]
     lib.vps_png_deflate.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.vps_png_encode_bound_bpp.argtypes = [c_int, c_int64, c_int, POINTER(c_int64), POINTER(c_int64)]
+    lib.vps_png_deflate_bpp.argtypes = [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.vps_kitti_flow_reconstruct_ws.argtypes = [c_int, c_int, POINTER(c_int64)]
+    lib.vps_kitti_flow_reconstruct.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.vps_kitti_flow_encode.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]
     lib.vps_rpn_select.argtypes = [POINTER(c_void_p), POINTER(c_int32), POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
                                    POINTER(c_float), c_int, c_int, c_void_p, c_int, POINTER(c_float), c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.vps_rpn_collect.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
