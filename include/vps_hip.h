@@ -108,8 +108,8 @@ typedef struct vps_conv_desc {
      * of 8) are ADDED to gn_stats[r][2 g], gn_stats[r][2 g + 1] (doubles; the caller zeroes all gn_rep copies; a block adds to
      * copy r = block index % gn_rep, gn_rep a power of two, so that the atomics of ~1000 blocks spread over gn_rep * 4 cache lines)
      * - the statistics pass of vps_groupnorm_relu without re-reading the tensor; finish with vps_groupnorm_apply, which adds the
-     * copies up. Deformable launches (offset != NULL) of the split-operand modes only, ksplit == 1, no residual,
-     * cout/out_ld/out_coff multiples of 4; VPS_EARG otherwise. */
+     * copies up. Deformable launches (offset != NULL) of the split-operand modes only, ksplit == 1, no residual, N == 1 (the sums
+     * have no image dimension: GroupNorm normalises per image), cout/out_ld/out_coff multiples of 4; VPS_EARG otherwise. */
     double* gn_stats;
     int32_t gn_cpg, gn_rep;
     /* ksplit > 1: int32 [nclass * tiles] tickets, ZERO on entry (the launch leaves them zero). Non-NULL: the block that finishes a

@@ -165,6 +165,10 @@ def deform_conv(x, offset, weight, stride=1, padding=1, dilation=1):
                 h_im = hs + i * dilation + off_h
                 w_im = ws + j * dilation + off_w
                 valid = (h_im > -1) & (w_im > -1) & (h_im < h) & (w_im < w)
+                # deform_conv_cuda_kernel.cu:225-237: a sample that fails the test keeps val = 0 and is never evaluated - selected
+                # here, not multiplied: a NaN or infinite offset must not reach the blend
+                h_im = torch.where(valid, h_im, torch.zeros_like(h_im))
+                w_im = torch.where(valid, w_im, torch.zeros_like(w_im))
                 h_low = torch.floor(h_im)
                 w_low = torch.floor(w_im)
                 lh = h_im - h_low
@@ -185,7 +189,8 @@ def deform_conv(x, offset, weight, stride=1, padding=1, dilation=1):
                 v3 = corner(h_high, w_low, (h_high <= h - 1) & (w_low >= 0))
                 v4 = corner(h_high, w_high, (h_high <= h - 1) & (w_high <= w - 1))
                 w1 = hh * hw; w2 = hh * lw; w3 = lh * hw; w4 = lh * lw
-                cols.append(w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4)          # [c, ho, wo]
+                col_t = w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4               # [c, ho, wo]
+                cols.append(torch.where(valid.unsqueeze(0), col_t, torch.zeros_like(col_t)))
         col = torch.stack(cols, dim=1).reshape(c * kh * kw, ho * wo)    # row = c*kh*kw + i*kw + j
         outs.append((weight.reshape(co, -1) @ col).view(co, ho, wo))
     return torch.stack(outs, 0)

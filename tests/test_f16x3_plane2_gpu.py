@@ -14,13 +14,10 @@ The weights hold what makes the derived plane differ from a careless one: one ou
 per-channel power-of-two scaling of PackedConv undoes those exactly), and, inside every channel, an eighth of the weights scaled by
 2^-14 (g0 * 2^-11 lands in the fp16 subnormals and is rounded there) and an eighth by 2^-26 (it underflows to zero).
 Deformable layer: integer offsets in [-2, 2], the same for the nine taps of a pixel (bilinear weights 1, 0, 0, 0: exact sampling)."""
-import json
-import subprocess
-
 import pytest
 import torch
 
-import test_conv_plan
+import conv_planner
 from vps_amd import hip, nhwc
 
 pytestmark = pytest.mark.gpu
@@ -54,23 +51,7 @@ CASES = [
 def planned_kernel(tmp_path_factory):
     """descriptor -> name of the kernel vpsi_conv_plan gives it: the stand-alone planner of tests/test_conv_plan.py (host C++), default
     switches, the limits recorded in tests/conv_plan_cases.json"""
-    table = json.load(open(test_conv_plan.TABLE))
-    tmp = tmp_path_factory.mktemp('plan')
-    test_conv_plan._plans(tmp, dict(int_fields=table['int_fields'], limits=table['limits'], rows=[]))      # compiles the driver
-    lim = table['limits']
-
-    def plan(d):
-        words = [lim['cus']] + lim['pw_per_cu'] + lim['thin_per_cu']
-        for f in table['int_fields']:
-            words.append(getattr(d, f[:-3])[int(f[-2])] if f.endswith(']') else getattr(d, f))
-        for f in test_conv_plan.POINTERS:
-            v = getattr(d, 'inp' if f == 'in' else f)
-            words.append(16 + (v & 15) if v else 0)
-        words += [1] * len(test_conv_plan.SWITCHES)
-        out = subprocess.run([str(tmp / 'plan_driver')], input=' '.join(str(w) for w in words), capture_output=True, text=True, check=True).stdout.split()
-        assert int(out[4]) == 0, out
-        return out[0]
-    return plan
+    return conv_planner.planned_kernel(tmp_path_factory.mktemp('plan'))
 
 
 def _weights(cin, cout, k, transposed, g):

@@ -144,7 +144,8 @@ int vpsi_conv_check(const vps_conv_desc& d) {
     // the split-operand kernels address the input and the weights through 32-bit buffer offsets
     if (d.prec != VPS_PREC_F32 && in_bytes(d) >= 0xFFFFFFF0ull) return VPS_EARG(16);
     // GroupNorm sums in the epilogue: the deformable kernel of the split-operand modes only, unsplit, float4 stores, groups of 4 | 8 | 16 ...
-    if (d.gn_stats && (!d.offset || d.prec == VPS_PREC_F32 || d.ksplit != 1 || d.gn_rep < 1 || (d.gn_rep & (d.gn_rep - 1)) || (d.gn_cpg != 4 && (d.gn_cpg < 8 || (d.gn_cpg & 7))) || d.cout % d.gn_cpg ||
+    // One image: the slot has no image dimension, and GroupNorm normalises per image
+    if (d.gn_stats && (!d.offset || d.N != 1 ||d.prec == VPS_PREC_F32 || d.ksplit != 1 || d.gn_rep < 1 || (d.gn_rep & (d.gn_rep - 1)) || (d.gn_cpg != 4 && (d.gn_cpg < 8 || (d.gn_cpg & 7))) || d.cout % d.gn_cpg ||
                        ((d.cout | d.out_ld | d.out_coff) & 3) || ((uintptr_t)d.out & 15) || d.res || ((uintptr_t)d.gn_stats & 7)))
         return VPS_EARG(15);
     const long Ml = (long)d.N * d.Qh * d.Qw;

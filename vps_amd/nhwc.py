@@ -354,7 +354,8 @@ def conv_geometry(layer, N, Qh, Qw, out_ld, out_coff, has_res, gn_groups):
             per = (ksteps + ksplit - 1) // ksplit
             ksplit = (ksteps + per - 1) // per
     gn_cpg = 0
-    if (gn_groups is not None and layer.deform and layer.prec != hip.PREC_F32 and ksplit == 1 and not has_res
+    # (one image only: the slot holds one set of sums, and GroupNorm normalises per image)
+    if (gn_groups is not None and N == 1 and layer.deform and layer.prec != hip.PREC_F32 and ksplit == 1 and not has_res
             and not ((layer.cout | out_ld | out_coff) & 3) and layer.cout % gn_groups == 0):
         cpg = layer.cout // gn_groups
         gn_cpg = cpg if cpg == 4 or cpg % 8 == 0 else 0
