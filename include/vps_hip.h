@@ -711,6 +711,7 @@ int vps_stq_lds_cells(void);
  *                caller-owned; the call ADDS to them and never zeroes them (as vps_stq_accumulate)
  *   flicker      NULL, or DEVICE uint8 [H][W], every byte written: 0 agrees, 1 class differs, 2 same class and both keys listed and
  *                different, 3 not in view
+ * The warp rule below, and its corners, weights and sample further down (vps_flow_occlusion), are implemented once: csrc/warp_rule.h.
  * Per pixel p = (x, y) of cur, fp32: sx = float(x) + u, sy = float(y) + v, qx = floorf(sx + 0.5f), qy = floorf(sy + 0.5f); in view iff
  * 0 <= qx <= W-1 and 0 <= qy <= H-1 as floats (NaN, inf fall out), else misc[1] += 1 and nothing else. In view, a = cur[p], b = prev[q]:
  * misc[0] += 1, conf[c(b)][c(a)] += 1, cur_size[k] += 1 when a's key is listed, prev_size[k] += 1 when b's is, same[k] += 1 when both are

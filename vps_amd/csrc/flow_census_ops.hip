@@ -6,8 +6,8 @@
 //   vps_flow_census           one (cur, prev, flow) triple: every pixel is ADDED to the caller's int64 [2][13] table; optionally the mask
 //                             with the flagged pixels (code 3) and the residual image are written. Nothing is zeroed, downloaded or
 //                             synchronised. Two launches:
-//     pass 1 (warp)    a lane owns 4 consecutive pixels (px4.h), as flow_photo_ops.hip: the in-view rule, the four corners of prev, the
-//                      bilinear sample of their greys in fp32 -> plane 0 (Wg, -1.0f = none); the greys of cur and prev -> planes 1, 2.
+//     pass 1 (warp)    a lane owns 4 consecutive pixels (px4.h), as flow_photo_ops.hip: the warp rule (warp_rule.h) on the greys of the
+//                      four corners of prev -> plane 0 (Wg, -1.0f = none); the greys of cur and prev -> planes 1, 2.
 //                      Read per pixel 3 + 3 + 8 bytes and the corner bytes from the cache, written 12.
 //     pass 2 (census)  a workgroup takes a tile of 32 rows x 64 columns: it stages the three planes with a halo of 3 in LDS (38 rows x 72
 //                      columns x 3 planes x 4 bytes = 32 832 bytes; positions outside the image are -1.0f = none), then every lane forms
@@ -16,16 +16,17 @@
 // Arithmetic: greys are integers up to 255 000, exact in fp32; the sample and the code differences are fp32 operations rounded on their
 // own (the file is compiled without contraction); every decision after the codes is an integer one, so the table, mask_out and residual
 // equal the NumPy restatement (tests/flow_census_restate.py) bit for bit. Integer atomics only: no finishing launch, the same bytes on
-// every call. No index is formed from a float before the in-view test has passed, and every corner address of `prev` is clamped.
+// every call.
 // Register blocking: the 4 pixels of a lane lie side by side in a row, so one window row of a plane is 10 values for 4 pixels, read as
 // three 16-byte LDS loads (12 values) instead of 4 x 7: 63 LDS loads per plane set and lane strip where the plain form has 588.
 #include "px4.h"
+#include "warp_rule.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int FC_THREADS = 256;
+constexpr int FC_THREADS = PX4_WG;
 constexpr int FC_TR = 32, FC_TC = 64;                  // the tile of pass 2
 constexpr int FC_R = 3;                                // the window is (2 FC_R + 1)^2
 constexpr int FC_PAD = 4;                              // columns staged on either side: the halo of 3 and one more, so that a lane's row is 16-byte aligned
@@ -48,7 +49,6 @@ __global__ __launch_bounds__(FC_THREADS)
 void flow_census_warp_kernel(const uint8_t* __restrict__ cur, const uint8_t* __restrict__ prev, int H, int W, const float* __restrict__ flow, int fld,
                              int fcoff, int fmode, float* __restrict__ wg, float* __restrict__ gc, float* __restrict__ gp) {
     const long npix = (long)H * W, nchunk = (npix + PX4 - 1) / PX4;
-    const float xmax = (float)(W - 1), ymax = (float)(H - 1);
     for (long ch = (long)blockIdx.x * FC_THREADS + threadIdx.x; ch < nchunk; ch += (long)gridDim.x * FC_THREADS) {
         const long p0 = PX4 * ch;
         const int n = (int)min((long)PX4, npix - p0);
@@ -64,19 +64,11 @@ void flow_census_warp_kernel(const uint8_t* __restrict__ cur, const uint8_t* __r
             oc[i] = fc_grey(c4[i] & 0xffu, (c4[i] >> 8) & 0xffu, c4[i] >> 16);
             op[i] = fc_grey(s4[i] & 0xffu, (s4[i] >> 8) & 0xffu, s4[i] >> 16);
             if (i < n) {
-                const float sx = (float)x + u[i], sy = (float)y + v[i];
-                const float qx = floorf(sx + 0.5f), qy = floorf(sy + 0.5f);
-                const bool in = qx >= 0.f && qx <= xmax && qy >= 0.f && qy <= ymax;    // as floats: NaN, +-inf, 1e30 fall out here
-                if (in) {
-                    const float x0 = floorf(sx), y0 = floorf(sy);                      // -1 .. W-1 resp. -1 .. H-1 once in view
-                    const float wx = sx - x0, wy = sy - y0;
-                    const float x1 = x0 + 1.f, y1 = y0 + 1.f;
-                    const int ix0 = min(max((int)x0, 0), W - 1), ix1 = min(max((int)x1, 0), W - 1);
-                    const int iy0 = min(max((int)y0, 0), H - 1), iy1 = min(max((int)y1, 0), H - 1);
-                    const float g00 = fc_corner(prev, W, iy0, ix0), g01 = fc_corner(prev, W, iy0, ix1);
-                    const float g10 = fc_corner(prev, W, iy1, ix0), g11 = fc_corner(prev, W, iy1, ix1);
-                    const float top = g00 + wx * (g01 - g00), bot = g10 + wx * (g11 - g10);
-                    ow[i] = top + wy * (bot - top);
+                const float sx = warp_pos(x, u[i]), sy = warp_pos(y, v[i]);             // warp_rule.h: in view, corners, sample
+                if (warp_in_view(sx, sy, W, H)) {
+                    const WarpCorners k = warp_corners(sx, sy, W, H);
+                    ow[i] = warp_lerp2(fc_corner(prev, W, k.y0, k.x0), fc_corner(prev, W, k.y0, k.x1), fc_corner(prev, W, k.y1, k.x0),
+                                       fc_corner(prev, W, k.y1, k.x1), k.wx, k.wy);
                 }
                 if (++x == W) { x = 0; ++y; }
             }
@@ -195,20 +187,8 @@ void flow_census_kernel(const float* __restrict__ wg, const float* __restrict__ 
         if (mask_out) px4_store_bytes(mask_out, ((uintptr_t)(mask_out + p0) & 3) == 0, p0, n, codes);
         if (residual) px4_store_bytes(residual, ((uintptr_t)(residual + p0) & 3) == 0, p0, n, resid);
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int g = 0; g < 2; ++g)
-#pragma unroll
-        for (int k = 0; k < FC_CELLS; ++k) {
-            const uint32_t s = wave_sum(cnt[g][k]);    // at most 2048 pixels x 48: far from 2^32
-            if (lane == 0) red[wave][g * FC_CELLS + k] = s;
-        }
-    __syncthreads();
-    if (threadIdx.x < 2 * FC_CELLS) {
-        unsigned long long c = 0;
-        for (int w = 0; w < FC_THREADS / 64; ++w) c += red[w][threadIdx.x];
-        if (c) atomicAdd(&table[threadIdx.x], c);
-    }
+    // the two rows are the table's 26 cells in order (declared flat, the kernel takes 6 more SGPRs); a cell: at most 2048 pixels x 48
+    wg_counts_to_table(reinterpret_cast<const uint32_t(&)[2 * FC_CELLS]>(cnt), red, table);
 }
 
 }  // namespace

@@ -15,16 +15,9 @@
 
 namespace {
 
-constexpr int FE_THREADS = 256;
-constexpr int FE_MAX_GROUPS = 1024;                   // workgroups of the counting launch = slots of the workspace (4 per CU, then grid-stride)
+constexpr int FE_THREADS = PX4_WG;
 constexpr int FE_CELLS = 25, FE_SUMS = 8;
 constexpr double FE_UNKNOWN = 1e9;                    // the Middlebury convention of vps_flow_max_radius
-
-long fe_groups(long npix) {
-    const long nchunk = (npix + PX4 - 1) / PX4;
-    long g = (nchunk + FE_THREADS - 1) / FE_THREADS;
-    return g > FE_MAX_GROUPS ? FE_MAX_GROUPS : g;
-}
 
 // the row of the error-colour table, R | G << 8 | B << 16
 __device__ __forceinline__ uint32_t fe_colour(double n_err) {
@@ -44,10 +37,9 @@ __device__ __forceinline__ uint32_t fe_colour(double n_err) {
 }
 
 // A lane owns 4 consecutive pixels (linear index) per step; a workgroup strides over the chunks. The 25 counters (uint32: H W < 2^31) and the
-// 8 sums of a lane stay in registers under constant indices; at the end they are summed across the wavefront by xor shuffles (a fixed
-// tree) and across the four wavefronts in LDS in a fixed order. The counts leave as one 64-bit atomic per non-zero cell, the sums as the
-// workgroup's own slot of `slots` (always written, zeros too: the finishing launch reads every slot). No workgroup reads what another
-// one writes.
+// 8 sums of a lane stay in registers under constant indices; they leave in the order of the tables through Part C of px4.h: the counts
+// as one 64-bit atomic per non-zero cell, the sums as the workgroup's own slot of `slots` (always written, zeros too: the finishing
+// launch reads every slot). No workgroup reads what another one writes.
 __global__ __launch_bounds__(FE_THREADS)
 void flow_error_kernel(const float* __restrict__ pred, int pld, int pcoff, int pmode, const float* __restrict__ gt, int gld, int gcoff, int gmode,
                        const uint8_t* __restrict__ mask, const uint8_t* __restrict__ occ_pred, long npix, unsigned long long* __restrict__ counts,
@@ -118,53 +110,25 @@ void flow_error_kernel(const float* __restrict__ pred, int pld, int pcoff, int p
         }
         if (rgb) px4_store_px3(rgb, rgb4, p0, n, col);
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t cell[FE_CELLS];                          // the tables' order (flat arrays through the loop cost 5 VGPRs and a wave of occupancy)
+    double tot[FE_SUMS];
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
 #pragma unroll
-        for (int k = 0; k < 12; ++k) {
-            const uint32_t c = wave_sum(cnt[g][k]);
-            if (lane == 0) red_c[wave][g * 12 + k] = c;
-        }
+        for (int k = 0; k < 12; ++k) cell[g * 12 + k] = cnt[g][k];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const double s = wave_sum(sum[g][k]);                                     // s(l) + s(l ^ off): the same tree in every lane
-            if (lane == 0) red_s[wave][g * 4 + k] = s;
-        }
+        for (int k = 0; k < 4; ++k) tot[g * 4 + k] = sum[g][k];
     }
-    n_inv = wave_sum(n_inv);
-    if (lane == 0) red_c[wave][24] = n_inv;
-    __syncthreads();
-    if (threadIdx.x < FE_CELLS) {
-        uint32_t c = 0;
-        for (int w = 0; w < FE_THREADS / 64; ++w) c += red_c[w][threadIdx.x];
-        if (c) atomicAdd(&counts[threadIdx.x], (unsigned long long)c);
-    }
-    if (threadIdx.x >= 64 && threadIdx.x < 64 + FE_SUMS) {
-        const int k = threadIdx.x - 64;
-        slots[(long)blockIdx.x * FE_SUMS + k] = (red_s[0][k] + red_s[1][k]) + (red_s[2][k] + red_s[3][k]);
-    }
-}
-
-// ONE workgroup: lane t owns cell t & 7 and adds the slots t >> 3, t >> 3 + 32, ... in ascending order; the 32 lanes of a cell are then
-// summed in a fixed tree (xor shuffles over 8, 16, 32, then the four wavefronts in order) and the eight totals are added to `sums`.
-__global__ __launch_bounds__(FE_THREADS)
-void flow_error_finish_kernel(const double* __restrict__ slots, int nslots, double* __restrict__ sums) {
-    __shared__ double part[FE_THREADS / 64][FE_SUMS];
-    const int k = threadIdx.x & 7;
-    double s = 0.0;
-    for (int j = threadIdx.x >> 3; j < nslots; j += FE_THREADS / FE_SUMS) s += slots[(long)j * FE_SUMS + k];
-    for (int off = 8; off <= 32; off <<= 1) s += __shfl_xor(s, off, 64);
-    if ((threadIdx.x & 63) < FE_SUMS) part[threadIdx.x >> 6][k] = s;
-    __syncthreads();
-    if (threadIdx.x < FE_SUMS) sums[k] = sums[k] + ((part[0][k] + part[1][k]) + (part[2][k] + part[3][k]));
+    cell[24] = n_inv;
+    wg_counts_to_table(cell, red_c, counts);
+    wg_sums_to_slot(tot, red_s, slots);
 }
 
 }  // namespace
 
 extern "C" int64_t vps_flow_error_ws_bytes(int H, int W) {
     if (H < 1 || W < 1 || (long)H * W >= (1L << 31)) return VPS_EARG(2);
-    return (int64_t)(fe_groups((long)H * W) * FE_SUMS * sizeof(double));
+    return px4_slot_bytes(px4_groups((long)H * W), FE_SUMS);
 }
 
 extern "C" int vps_flow_error(const float* pred, int pred_ld, int pred_coff, const float* gt, int gt_ld, int gt_coff, const uint8_t* mask,
@@ -174,14 +138,14 @@ extern "C" int vps_flow_error(const float* pred, int pred_ld, int pred_coff, con
     if (H < 1 || W < 1 || (long)H * W >= (1L << 31)) return VPS_EARG(2);           // a lane's uint32 counts cannot wrap
     if (pred_coff < 0 || pred_ld < pred_coff + 2 || gt_coff < 0 || gt_ld < gt_coff + 2) return VPS_EARG(3);
     if ((((uintptr_t)counts | (uintptr_t)sums) & 7) || (((uintptr_t)pred | (uintptr_t)gt) & 3)) return VPS_EARG(4);
-    const long npix = (long)H * W, g = fe_groups(npix);
-    if (((uintptr_t)ws & 7) || ws_bytes < (int64_t)(g * FE_SUMS * sizeof(double))) return VPS_EARG(5);
+    const long npix = (long)H * W, g = px4_groups(npix);
+    if (((uintptr_t)ws & 7) || ws_bytes < px4_slot_bytes(g, FE_SUMS)) return VPS_EARG(5);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(flow_error_kernel, dim3((unsigned)g), dim3(FE_THREADS), 0, s, pred, pred_ld, pred_coff, px4_flow_mode(pred, pred_ld, pred_coff), gt,
                        gt_ld, gt_coff, px4_flow_mode(gt, gt_ld, gt_coff), mask, occ_pred, npix, reinterpret_cast<unsigned long long*>(counts),
                        static_cast<double*>(ws), err_rgb);
     int st = vps_launch_status();
     if (st) return st;
-    hipLaunchKernelGGL(flow_error_finish_kernel, dim3(1), dim3(FE_THREADS), 0, s, static_cast<const double*>(ws), (int)g, sums);
+    hipLaunchKernelGGL(slot_finish_kernel<FE_SUMS>, dim3(1), dim3(PX4_WG), 0, s, static_cast<const double*>(ws), (int)g, sums);
     return vps_launch_status();
 }

@@ -5,15 +5,15 @@
 // Arithmetic: fp32, the operations of the definition (vps_amd/tc.py, include/vps_hip.h) in its order, every one rounded on its own - the
 // whole file is compiled without contraction, so that the mask equals the NumPy float32 restatement (tests/flow_occ_restate.py) on every
 // pixel: d2 <= thr sits on the boundary for whole-pixel shifts against a zero flow, where a fused multiply-add decides differently.
-// No index is formed from a float before the in-view test has passed, and every address of `back` is clamped to the map: NaN, inf and
-// 1e30 flows read nothing outside it.
+// The in-view test, the corners and the sample are warp_rule.h, the one implementation: NaN, inf and 1e30 flows read nothing outside `back`.
 #include "px4.h"
+#include "warp_rule.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int OCC_THREADS = 256;
+constexpr int OCC_THREADS = PX4_WG;
 
 __device__ __forceinline__ float2 occ_load2(const float* __restrict__ f, bool pair) {
     if (pair) return *reinterpret_cast<const float2*>(f);
@@ -30,7 +30,6 @@ void flow_occlusion_kernel(const float* __restrict__ fwd, int fld, int fcoff, in
                            int bpair, int H, int W, float alpha, float beta, uint8_t* __restrict__ occ, unsigned long long* __restrict__ counts) {
     __shared__ uint32_t red[OCC_THREADS / 64][3];
     const long npix = (long)H * W, nchunk = (npix + PX4 - 1) / PX4;
-    const float xmax = (float)(W - 1), ymax = (float)(H - 1);
     const bool occ4 = occ && ((uintptr_t)occ & 3) == 0;
     uint32_t cnt[3] = {0, 0, 0};
     for (long ch = (long)blockIdx.x * OCC_THREADS + threadIdx.x; ch < nchunk; ch += (long)gridDim.x * OCC_THREADS) {
@@ -43,23 +42,17 @@ void flow_occlusion_kernel(const float* __restrict__ fwd, int fld, int fcoff, in
 #pragma unroll
         for (int i = 0; i < PX4; ++i) {
             if (i >= n) break;
-            // ---- the definition, in its order
-            const float sx = (float)x + u[i], sy = (float)y + v[i];
-            const float qx = floorf(sx + 0.5f), qy = floorf(sy + 0.5f);
-            const bool in = qx >= 0.f && qx <= xmax && qy >= 0.f && qy <= ymax;    // as floats: NaN, +-inf, 1e30 fall out here
+            // ---- the definition, in its order (warp_rule.h: in view, corners, sample)
+            const float sx = warp_pos(x, u[i]), sy = warp_pos(y, v[i]);
             uint32_t code = 2;
-            if (in) {
-                const float x0 = floorf(sx), y0 = floorf(sy);                      // -1 .. W-1 resp. -1 .. H-1 once in view
-                const float wx = sx - x0, wy = sy - y0;
-                const float x1 = x0 + 1.f, y1 = y0 + 1.f;
-                const int ix0 = min(max((int)x0, 0), W - 1), ix1 = min(max((int)x1, 0), W - 1);
-                const int iy0 = min(max((int)y0, 0), H - 1), iy1 = min(max((int)y1, 0), H - 1);
-                const float* r0 = back + (long)iy0 * W * bld + bcoff;
-                const float* r1 = back + (long)iy1 * W * bld + bcoff;
-                const float2 b00 = occ_load2(r0 + (long)ix0 * bld, bpair), b01 = occ_load2(r0 + (long)ix1 * bld, bpair);
-                const float2 b10 = occ_load2(r1 + (long)ix0 * bld, bpair), b11 = occ_load2(r1 + (long)ix1 * bld, bpair);
-                const float top_u = b00.x + wx * (b01.x - b00.x), bot_u = b10.x + wx * (b11.x - b10.x), bt_u = top_u + wy * (bot_u - top_u);
-                const float top_v = b00.y + wx * (b01.y - b00.y), bot_v = b10.y + wx * (b11.y - b10.y), bt_v = top_v + wy * (bot_v - top_v);
+            if (warp_in_view(sx, sy, W, H)) {
+                const WarpCorners c = warp_corners(sx, sy, W, H);
+                const float* r0 = back + (long)c.y0 * W * bld + bcoff;
+                const float* r1 = back + (long)c.y1 * W * bld + bcoff;
+                const float2 b00 = occ_load2(r0 + (long)c.x0 * bld, bpair), b01 = occ_load2(r0 + (long)c.x1 * bld, bpair);
+                const float2 b10 = occ_load2(r1 + (long)c.x0 * bld, bpair), b11 = occ_load2(r1 + (long)c.x1 * bld, bpair);
+                const float bt_u = warp_lerp2(b00.x, b01.x, b10.x, b11.x, c.wx, c.wy);
+                const float bt_v = warp_lerp2(b00.y, b01.y, b10.y, b11.y, c.wx, c.wy);
                 const float dx = u[i] + bt_u, dy = v[i] + bt_v;
                 const float d2 = dx * dx + dy * dy;
                 const float m = (u[i] * u[i] + v[i] * v[i]) + (bt_u * bt_u + bt_v * bt_v);
@@ -73,16 +66,7 @@ void flow_occlusion_kernel(const float* __restrict__ fwd, int fld, int fcoff, in
         if (occ) px4_store_bytes(occ, occ4, p0, n, codes);
     }
     if (!counts) return;                                                           // uniform: a kernel argument
-#pragma unroll
-    for (int k = 0; k < 3; ++k) cnt[k] = wave_sum(cnt[k]);
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 3; ++k) red[threadIdx.x >> 6][k] = cnt[k];
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        uint32_t s = 0;
-        for (int w = 0; w < OCC_THREADS / 64; ++w) s += red[w][threadIdx.x];
-        if (s) atomicAdd(&counts[threadIdx.x], (unsigned long long)s);
-    }
+    wg_counts_to_table(cnt, red, counts);
 }
 
 }  // namespace

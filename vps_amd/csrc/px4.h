@@ -2,6 +2,7 @@
 // flow_occ_ops.hip, flow_err_ops.hip, sseg_confusion_kernel of ipq_ops.hip). Chunk ch holds pixels 4 ch .. 4 ch + n - 1 (linear index,
 // n < 4 only in the last one). Everything that decides whether a kernel reads or writes outside a buffer is here, once.
 // Part A is integer and address work only and also compiles as plain C++: tests/test_px4_host.py runs it under the host sanitizers.
+// Part C is how a workgroup's counters and sums reach the caller's tables (flow_occ, flow_err, flow_photo, flow_census): once.
 #pragma once
 #include <stdint.h>
 #ifdef __HIPCC__
@@ -159,5 +160,67 @@ __device__ __forceinline__ bool wave_same_run(bool has, uint64_t key, uint32_t l
     if (__ballot(has && key != first)) return false;
     sum = wave_sum(has ? len : 0u);
     return true;
+}
+#endif
+
+// ---------------------------------------------------------------------------------------------- Part C: the workgroup's tables
+// How a lane's counters and sums leave a workgroup of PX4_WG lanes: summed over the wavefront into one LDS row per wavefront, then
+// the counts as one 64-bit atomic per non-zero cell and the sums, without any floating-point atomic, as the workgroup's own slot.
+constexpr int PX4_WG = 256;
+constexpr int PX4_MAX_GROUPS = 1024;                  // workgroups of a launch with slots = slots of its workspace (4 per CU, then grid-stride)
+
+static inline long px4_groups(long npix) {
+    const long nchunk = (npix + PX4 - 1) / PX4, g = (nchunk + PX4_WG - 1) / PX4_WG;
+    return g > PX4_MAX_GROUPS ? PX4_MAX_GROUPS : g;
+}
+
+static inline int64_t px4_slot_bytes(long groups, int nsum) { return (int64_t)(groups * nsum * sizeof(double)); }
+
+#ifdef __HIPCC__
+template <int N, class T>
+__device__ __forceinline__ void wg_rows(const T (&cell)[N], T (&red)[PX4_WG / 64][N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const T s = wave_sum(cell[k]);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s;
+    }
+    __syncthreads();
+}
+
+// T: uint32_t or unsigned long long; a workgroup's total of a cell fits it (the callers bound their pixels)
+template <int NCELL, class T>
+__device__ __forceinline__ void wg_counts_to_table(const T (&cell)[NCELL], T (&red)[PX4_WG / 64][NCELL], unsigned long long* __restrict__ table) {
+    wg_rows(cell, red);
+    if (threadIdx.x < NCELL) {
+        T c = 0;
+        for (int w = 0; w < PX4_WG / 64; ++w) c += red[w][threadIdx.x];
+        if (c) atomicAdd(&table[threadIdx.x], (unsigned long long)c);
+    }
+}
+
+// lanes 64 .. 64 + NSUM - 1 write the slot, zeros too: the finishing launch reads every slot
+template <int NSUM>
+__device__ __forceinline__ void wg_sums_to_slot(const double (&sum)[NSUM], double (&red)[PX4_WG / 64][NSUM], double* __restrict__ slots) {
+    wg_rows(sum, red);
+    if (threadIdx.x >= 64 && threadIdx.x < 64 + NSUM) {
+        const int k = threadIdx.x - 64;
+        slots[(long)blockIdx.x * NSUM + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+    }
+}
+
+// ONE workgroup: lane t owns cell t % NSUM and adds the slots t / NSUM, + PX4_WG / NSUM, ... in ascending order; a cell's lanes are then
+// summed in a fixed tree (xor shuffles over NSUM .. 32, then the four wavefronts in order) and the totals are added to `sums`.
+template <int NSUM>
+__global__ __launch_bounds__(PX4_WG)
+void slot_finish_kernel(const double* __restrict__ slots, int nslots, double* __restrict__ sums) {
+    static_assert(PX4_WG == 256 && NSUM <= 32 && (NSUM & (NSUM - 1)) == 0, "four wavefronts; a cell's lanes are an xor class");
+    __shared__ double part[PX4_WG / 64][NSUM];
+    const int k = threadIdx.x % NSUM;
+    double s = 0.0;
+    for (int j = threadIdx.x / NSUM; j < nslots; j += PX4_WG / NSUM) s += slots[(long)j * NSUM + k];
+    for (int off = NSUM; off <= 32; off <<= 1) s += __shfl_xor(s, off, 64);
+    if ((threadIdx.x & 63) < NSUM) part[threadIdx.x >> 6][k] = s;
+    __syncthreads();
+    if (threadIdx.x < NSUM) sums[k] = sums[k] + ((part[0][k] + part[1][k]) + (part[2][k] + part[3][k]));
 }
 #endif

@@ -5,8 +5,10 @@
 //                          pixel disagrees. The tables stay on the device; nothing is zeroed, downloaded or synchronised here.
 //   vps_tc_accumulate_masked   the same with a byte mask (vps_flow_occlusion's): an in-view pixel whose mask byte is not 0 is counted in
 //                          one extra cell and in nothing else
+// Where a pixel lands and whether that is in view: warp_rule.h (warp_nearest), the one implementation.
 // Integer adds only: the result does not depend on their order, so two runs (and the two table paths) give identical tables.
 #include "px4.h"
+#include "warp_rule.h"
 #include <string.h>
 
 namespace {
@@ -60,7 +62,6 @@ void tc_accumulate_kernel(const uint8_t* __restrict__ prev, const uint8_t* __res
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const long npix = (long)H * W, nbytes = 3 * npix, nchunk = (npix + PX4 - 1) / PX4;
-    const float xmax = (float)(W - 1), ymax = (float)(H - 1);
     const int sh = 8 * idch;
     const bool flick4 = flick && ((uintptr_t)flick & 3) == 0;
     uint32_t n_in = 0, n_out = 0, n_msk = 0;
@@ -82,15 +83,9 @@ void tc_accumulate_kernel(const uint8_t* __restrict__ prev, const uint8_t* __res
 #pragma unroll
             for (int i = 0; i < PX4; ++i) {
                 if (i >= n) break;
-                // ---- the definition's warp: fp32, one add each, compared as floats before any conversion
-                const float sx = (float)x + u[i], sy = (float)y + v[i];
-                const float qx = floorf(sx + 0.5f), qy = floorf(sy + 0.5f);
-                bool in = qx >= 0.f && qx <= xmax && qy >= 0.f && qy <= ymax;
-                int ix = 0, iy = 0;
-                if (in) {
-                    ix = (int)qx; iy = (int)qy;
-                    in = ix < W && iy < H;            // (float)(W - 1) is W itself for some W above 2^24: never read past the map
-                }
+                // ---- the definition's warp (warp_rule.h): fp32, one add each, compared as floats before any conversion
+                int ix, iy;
+                bool in = warp_nearest(warp_pos(x, u[i]), warp_pos(y, v[i]), W, H, ix, iy);
                 const bool msk = MASKED && in && ((M >> (8 * i)) & 0xffu) != 0;
                 if (msk) in = false;                  // from here on: in = in view and counted
                 uint32_t st = 0;

@@ -38,13 +38,10 @@ size is no multiple of 64 (a 436 x 1024 Sintel frame needs padding that `FlowNet
 `vps_flow_error`: no CPU path, the HIP library must load and a device must be present; host arrays are uploaded, device flows (`FMap`,
 [H,W,2], [1,2,H,W]: `pano_results['flow']`, `flow_between`) are used where they lie. The sums are reproducible byte for byte: no
 floating-point atomics (include/vps_hip.h)."""
-import json
-import os
-
 import numpy as np
 import torch
 
-from . import flowvis, hip
+from . import flowvis, hip, pairtables
 
 COUNT_CELLS, SUM_CELLS = 25, 8
 ERROR_COLOURS = ((0.1875, (49, 54, 149)), (0.375, (69, 117, 180)), (0.75, (116, 173, 209)), (1.5, (171, 217, 233)), (3.0, (224, 243, 248)),
@@ -150,15 +147,6 @@ def _device_flow(f, device):
     return flowvis._flow_view(f)
 
 
-def _byte_map(m, H, W, device, what):
-    if m is None:
-        return None
-    t = torch.from_numpy(np.ascontiguousarray(m)) if isinstance(m, np.ndarray) else m
-    if not (torch.is_tensor(t) and t.dtype == torch.uint8 and tuple(t.shape) == (H, W)):
-        raise ValueError('%s is uint8 [%d,%d] like the flows, got %s %s' % (what, H, W, getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
-    return t.to(device).contiguous()
-
-
 def _accumulate(pred, gt, mask, occ_pred, counts, sums, err_rgb, device):
     """one `vps_flow_error` on the current stream into the caller's device tables; returns the error image or None"""
     lib = hip.load()
@@ -166,15 +154,13 @@ def _accumulate(pred, gt, mask, occ_pred, counts, sums, err_rgb, device):
     gtt, gld, gco, gH, gW = _device_flow(gt, device)
     if (gH, gW) != (H, W):
         raise ValueError('pred and gt must have equal H, W: pred %s, gt %s' % ((H, W), (gH, gW)))
-    mask = _byte_map(mask, H, W, device, 'mask')
-    occ_pred = _byte_map(occ_pred, H, W, device, 'occ_pred')
+    mask = pairtables.byte_map(mask, H, W, device, 'mask', 'flows')
+    occ_pred = pairtables.byte_map(occ_pred, H, W, device, 'occ_pred', 'flows')
     if err_rgb is True:
         err_rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=device)
     elif err_rgb is False:
         err_rgb = None
-    if err_rgb is not None and not (torch.is_tensor(err_rgb) and err_rgb.is_cuda and err_rgb.dtype == torch.uint8 and err_rgb.is_contiguous()
-                                    and tuple(err_rgb.shape) == (H, W, 3)):
-        raise ValueError('err_rgb is True, or a contiguous device uint8 [H,W,3] tensor')
+    pairtables.out_map(err_rgb, (H, W, 3), 'err_rgb is True, or a contiguous device uint8 [H,W,3] tensor')
     nbytes = int(lib.vps_flow_error_ws_bytes(H, W))
     hip.check(min(nbytes, 0), 'vps_flow_error_ws_bytes')
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=device)   # (stream-ordered: the allocator hands the block on only behind its last use)
@@ -184,10 +170,7 @@ def _accumulate(pred, gt, mask, occ_pred, counts, sums, err_rgb, device):
 
 
 def _device(device):
-    device = torch.device(device)
-    if device.type != 'cuda' or not torch.cuda.is_available():
-        raise hip.VpsHipError('the flow accuracy is counted on the device (vps_flow_error); there is no CPU path and no device is present')
-    return device
+    return pairtables.device_or_raise(device, 'the flow accuracy is counted on the device (vps_flow_error); there is no CPU path and no device is present')
 
 
 def flow_error(pred, gt, mask=None, occ_pred=None, err_rgb=False, device=None):
@@ -212,45 +195,30 @@ class FlowEvaluator(FlowEvalStats):
         self.device = _device(device)
         self.per_pair = bool(per_pair)
         self.lib = hip.load()
-        self._counts, self._sums, self._names, self._n = [], [], [], 0
-
-    def _row(self):
-        i = self._n if self.per_pair else 0              # the row this pair adds to
-        if i >= 16 * len(self._counts):                  # pairs come one by one: rows in blocks, still one download
-            rows = 16 if self.per_pair else 1
-            self._counts.append(torch.zeros((rows, COUNT_CELLS), dtype=torch.int64, device=self.device))
-            self._sums.append(torch.zeros((rows, SUM_CELLS), dtype=torch.float64, device=self.device))
-        return self._counts[i // 16][i % 16], self._sums[i // 16][i % 16]
+        self._tables = pairtables.PairTables(self.device, self.per_pair, [((COUNT_CELLS,), torch.int64), ((SUM_CELLS,), torch.float64)])
+        self._names = []
 
     def add_pair(self, pred, gt, mask=None, occ_pred=None, err_rgb=None, name=None):
         """count one pair; err_rgb: None, True or a contiguous device uint8 [H,W,3] tensor that receives the error image (returned).
         Every pair of a set comes with an occ_pred or none does. Nothing is downloaded."""
-        if self._n and (occ_pred is not None) != self.with_occ:
+        if self._tables.n and (occ_pred is not None) != self.with_occ:
             raise ValueError('a set is counted with a predicted occlusion mask for every pair or for none')
-        counts, sums = self._row()
+        counts, sums = self._tables.row()
         img = _accumulate(pred, gt, mask, occ_pred, counts, sums, False if err_rgb is None else err_rgb, self.device)
         self.with_occ = occ_pred is not None
-        self._names.append(str(self._n) if name is None else str(name))
-        self._n += 1
+        self._names.append(str(self._tables.n) if name is None else str(name))
+        self._tables.n += 1
         return img
 
     def result(self):
         """the one download (and synchronisation) of what `add_pair` has counted since the last call, then `FlowEvalStats.result`"""
-        if self._n:
-            counts = (torch.cat(self._counts) if len(self._counts) > 1 else self._counts[0]).cpu().numpy()
-            sums = (torch.cat(self._sums) if len(self._sums) > 1 else self._sums[0]).cpu().numpy()
-            if self.per_pair:
-                self.add_tables(counts[:self._n], sums[:self._n], self._n, self._names, self.with_occ)
-            else:
-                self.add_tables(counts[0], sums[0], self._n, None, self.with_occ)
-            self._counts, self._sums, self._names, self._n = [], [], [], 0
+        if self._tables.n:
+            n, (counts, sums) = self._tables.download()
+            names, self._names = self._names, []
+            self.add_tables(counts, sums, n, names if self.per_pair else None, self.with_occ)
         return super().result()
 
 
 def write_outputs(result, out_dir):
     """flow-eval.txt and flow-eval.json in `out_dir`"""
-    os.makedirs(out_dir, exist_ok=True)
-    with open(os.path.join(out_dir, 'flow-eval.txt'), 'w') as f:
-        f.write(flow_text(result))
-    with open(os.path.join(out_dir, 'flow-eval.json'), 'w') as f:
-        json.dump(result, f, indent=1)
+    pairtables.write_result(result, out_dir, 'flow-eval', flow_text(result))

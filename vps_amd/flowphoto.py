@@ -77,14 +77,12 @@ ce_static = sum d_s / sum n_s, ratio = ce_warp / ce_static, gain = ce_static - c
 flagged_share (shares of the scored pixels), outside (cell 11), alone (cell 12), outside_share = outside / (n + outside + alone).
 `census_from_tables`, `CensusStats`, `census_text` are NumPy / Python only; `flow_census` and `CensusEvaluator` are `vps_flow_census`:
 no CPU path."""
-import json
 import math
-import os
 
 import numpy as np
 import torch
 
-from . import hip
+from . import hip, pairtables
 from .tc import _flow_layout
 
 COUNT_CELLS, SUM_CELLS = 21, 4
@@ -225,38 +223,22 @@ def residual_colour(residual):
 
 # ---------------------------------------------------------------------------------------------- the device side
 def _device(device):
-    device = torch.device(device)
-    if device.type != 'cuda' or not torch.cuda.is_available():
-        raise hip.VpsHipError('the photometric error is counted on the device (vps_flow_photo); there is no CPU path and no device is present')
-    return device
+    return pairtables.device_or_raise(device, 'the photometric error is counted on the device (vps_flow_photo); there is no CPU path and no device is present')
 
 
-def _frame(f, H, W, device, what):
-    t = torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f
-    if not (torch.is_tensor(t) and t.dtype == torch.uint8 and tuple(t.shape) == (H, W, 3)):
-        raise ValueError('%s is a uint8 [%d,%d,3] frame of the flow\'s H, W, got %s %s' % (what, H, W, getattr(t, 'dtype', type(t)),
-                                                                                           tuple(getattr(t, 'shape', ()))))
-    return t.to(device).contiguous()
-
-
-def _out_map(t, H, W, what):
-    if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and tuple(t.shape) == (H, W)):
-        raise ValueError('%s is a contiguous device uint8 [%d,%d] tensor' % (what, H, W))
-    return t
+def _pair_inputs(cur, prev, flow, mask, mask_out, residual, device):
+    """the checks both kernels share -> (flow, ld, H, W, cur, prev, mask) on the device"""
+    flow, ld = _flow_layout(flow, device)
+    H, W = int(flow.shape[0]), int(flow.shape[1])
+    cur, prev = pairtables.frame(cur, H, W, device, 'cur'), pairtables.frame(prev, H, W, device, 'prev')
+    mask = pairtables.byte_map(mask, H, W, device, 'mask', 'flow')            # (a device mask is used where it lies: it may be mask_out)
+    for t, what in ((mask_out, 'mask_out'), (residual, 'residual')):
+        pairtables.out_map(t, (H, W), '%s is a contiguous device uint8 [%d,%d] tensor' % (what, H, W))
+    return flow, ld, H, W, cur, prev, mask
 
 
 def _accumulate(lib, cur, prev, flow, mask, thr, counts, sums, mask_out, residual, device):
-    flow, ld = _flow_layout(flow, device)
-    H, W = int(flow.shape[0]), int(flow.shape[1])
-    cur, prev = _frame(cur, H, W, device, 'cur'), _frame(prev, H, W, device, 'prev')
-    if mask is not None:
-        m = torch.from_numpy(np.ascontiguousarray(mask)) if isinstance(mask, np.ndarray) else mask
-        if not (torch.is_tensor(m) and m.dtype == torch.uint8 and tuple(m.shape) == (H, W)):
-            raise ValueError('mask is uint8 [%d,%d] like the flow, got %s %s' % (H, W, getattr(m, 'dtype', type(m)), tuple(getattr(m, 'shape', ()))))
-        keep = m.is_cuda and m.is_contiguous()
-        mask = m if keep else m.to(device).contiguous()                          # (a device mask is used where it lies: it may be mask_out)
-    _out_map(mask_out, H, W, 'mask_out')
-    _out_map(residual, H, W, 'residual')
+    flow, ld, H, W, cur, prev, mask = _pair_inputs(cur, prev, flow, mask, mask_out, residual, device)
     if not float(thr) >= 0:
         raise ValueError('thr is not negative, got %r' % (thr,))
     nbytes = int(lib.vps_flow_photo_ws_bytes(H, W))
@@ -287,59 +269,58 @@ def flow_photometric(cur, prev, flow, mask=None, thr=PHOTO_THR, counts=None, sum
     return counts, sums
 
 
-class PhotoEvaluator(PhotoStats):
-    """The device side. `add_pair` counts one pair into tables that stay on the device (`vps_flow_photo`, no synchronisation between
-    pairs); `end_video` is the ONE download of a video. per_pair=True: every pair gets its own row of the tables (in blocks of 16 rows,
-    still one download), the video's tables are the sum of the rows and `result()['per_pair']` has the figures of every pair."""
+class _VideoPairs:
+    """What `PhotoEvaluator` and `CensusEvaluator` share, in front of their Stats class: pairs are counted into `pairtables.PairTables`
+    (`_count_pair` is the one kernel call), a video is one download."""
 
-    def __init__(self, device='cuda', thr=PHOTO_THR, per_pair=False):
-        super().__init__(thr)
+    def _open(self, device, per_pair, specs):
         self.device = _device(device)
         self.per_pair = bool(per_pair)
         self.lib = hip.load()
-        self._counts, self._sums, self._n = [], [], 0
+        self._tables = pairtables.PairTables(self.device, self.per_pair, specs)
 
-    def _row(self):
-        i = self._n if self.per_pair else 0              # the row this pair adds to
-        if i >= 16 * len(self._counts):                  # pairs come one by one: rows in blocks, still one download
-            rows = 16 if self.per_pair else 1
-            self._counts.append(torch.zeros((rows, COUNT_CELLS), dtype=torch.int64, device=self.device))
-            self._sums.append(torch.zeros((rows, SUM_CELLS), dtype=torch.float64, device=self.device))
-        return self._counts[i // 16][i % 16], self._sums[i // 16][i % 16]
+    _n = property(lambda self: self._tables.n)           # the pairs of the open video
 
     def add_pair(self, prev_frame, cur_frame, flow, mask=None, residual=None):
         """count one pair into the open video (opened by the first pair). mask: None or uint8 [H,W], `tc.flow_occlusion`'s codes;
         residual: None or a contiguous device uint8 [H,W] tensor that receives the residual image. Nothing is downloaded."""
-        counts, sums = self._row()
-        _accumulate(self.lib, cur_frame, prev_frame, flow, mask, self.thr, counts, sums, None, residual, self.device)
-        self._n += 1
+        self._count_pair(cur_frame, prev_frame, flow, mask, residual, *self._tables.row())
+        self._tables.n += 1
 
     def end_video(self, video_id=None):
         """the one download (and synchronisation) of the open video; returns its entry"""
-        assert self._n, 'no video is open'
-        counts = (torch.cat(self._counts) if len(self._counts) > 1 else self._counts[0]).cpu().numpy()
-        sums = (torch.cat(self._sums) if len(self._sums) > 1 else self._sums[0]).cpu().numpy()
-        n = self._n
-        self._counts, self._sums, self._n = [], [], 0
-        if self.per_pair:
-            return self.add_tables(video_id, counts[:n], sums[:n], n)
-        return self.add_tables(video_id, counts[0], sums[0], n)
+        assert self._tables.n, 'no video is open'
+        n, tables = self._tables.download()
+        return self.add_tables(video_id, *tables, n)
 
     def add_video(self, frames, flows, video_id=None, masks=None, residuals=None):
         """frames: the frames of one video in order, uint8 [H,W,3]; flows: one per frame, flows[t] the flow of frame t to frame t-1
         (flows[0] is not used and may be None); masks, residuals: None or one entry (or None) per frame. Returns the video's entry."""
-        assert self._n == 0, 'a video opened by add_pair is not ended'
+        assert not self._tables.n, 'a video opened by add_pair is not ended'
         if len(flows) != len(frames) or any(x is not None and len(x) != len(frames) for x in (masks, residuals)):
             raise ValueError('one flow (mask, residual) per frame, the first is not used: %d frames, %d flows' % (len(frames), len(flows)))
         if len(frames) < 2:
-            return self.add_tables(video_id, np.zeros(COUNT_CELLS, dtype=np.int64), np.zeros(SUM_CELLS), 0)
+            return self.add_tables(video_id, *self._tables.zeros(), 0)
         for t in range(1, len(frames)):                  # no synchronisation between pairs
             self.add_pair(frames[t - 1], frames[t], flows[t], mask=None if masks is None else masks[t], residual=None if residuals is None else residuals[t])
         return self.end_video(video_id)
 
     def result(self):
-        assert self._n == 0, 'a video opened by add_pair is not ended'
+        assert not self._tables.n, 'a video opened by add_pair is not ended'
         return super().result()
+
+
+class PhotoEvaluator(_VideoPairs, PhotoStats):
+    """The device side. `add_pair` counts one pair into tables that stay on the device (`vps_flow_photo`, no synchronisation between
+    pairs); `end_video` is the ONE download of a video. per_pair=True: every pair gets its own row of the tables (in blocks of 16 rows,
+    still one download), the video's tables are the sum of the rows and `result()['per_pair']` has the figures of every pair."""
+
+    def __init__(self, device='cuda', thr=PHOTO_THR, per_pair=False):
+        PhotoStats.__init__(self, thr)
+        self._open(device, per_pair, [((COUNT_CELLS,), torch.int64), ((SUM_CELLS,), torch.float64)])
+
+    def _count_pair(self, cur, prev, flow, mask, residual, counts, sums):
+        _accumulate(self.lib, cur, prev, flow, mask, self.thr, counts, sums, None, residual, self.device)
 
 
 def score_videos(evaluator, frames, flows, names, nframes_per_video, back_flows=None, map_dir=None, alpha=128, quality=90, entropy='host'):
@@ -377,11 +358,7 @@ def score_videos(evaluator, frames, flows, names, nframes_per_video, back_flows=
 
 def write_outputs(result, out_dir):
     """flow-photo.txt and flow-photo.json in `out_dir`"""
-    os.makedirs(out_dir, exist_ok=True)
-    with open(os.path.join(out_dir, 'flow-photo.txt'), 'w') as f:
-        f.write(photo_text(result))
-    with open(os.path.join(out_dir, 'flow-photo.json'), 'w') as f:
-        json.dump(result, f, indent=1)
+    pairtables.write_result(result, out_dir, 'flow-photo', photo_text(result))
 
 
 # ---------------------------------------------------------------------------------------------- the ternary census residual (row 3i)
@@ -475,16 +452,7 @@ def census_text(result):
 
 def _census_accumulate(lib, cur, prev, flow, mask, thr, eps, table, mask_out, residual, device):
     thr, eps = _census_args(thr, eps)
-    flow, ld = _flow_layout(flow, device)
-    H, W = int(flow.shape[0]), int(flow.shape[1])
-    cur, prev = _frame(cur, H, W, device, 'cur'), _frame(prev, H, W, device, 'prev')
-    if mask is not None:
-        m = torch.from_numpy(np.ascontiguousarray(mask)) if isinstance(mask, np.ndarray) else mask
-        if not (torch.is_tensor(m) and m.dtype == torch.uint8 and tuple(m.shape) == (H, W)):
-            raise ValueError('mask is uint8 [%d,%d] like the flow, got %s %s' % (H, W, getattr(m, 'dtype', type(m)), tuple(getattr(m, 'shape', ()))))
-        mask = m if (m.is_cuda and m.is_contiguous()) else m.to(device).contiguous()     # (a device mask is used where it lies: it may be mask_out)
-    _out_map(mask_out, H, W, 'mask_out')
-    _out_map(residual, H, W, 'residual')
+    flow, ld, H, W, cur, prev, mask = _pair_inputs(cur, prev, flow, mask, mask_out, residual, device)
     nbytes = int(lib.vps_flow_census_ws_bytes(H, W))
     hip.check(min(nbytes, 0), 'vps_flow_census_ws_bytes')
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=device)            # (stream-ordered: the allocator hands the block on only behind its last use)
@@ -507,57 +475,19 @@ def flow_census(cur, prev, flow, mask=None, thr=CENSUS_THR, eps=CENSUS_EPS, tabl
     return table
 
 
-class CensusEvaluator(CensusStats):
+class CensusEvaluator(_VideoPairs, CensusStats):
     """The device side. `add_pair` counts one pair into a table that stays on the device (`vps_flow_census`, no synchronisation between
     pairs); `end_video` is the ONE download of a video. per_pair=True: every pair gets its own table (in blocks of 16, still one
     download), the video's table is their sum and `result()['per_pair']` has the figures of every pair."""
 
     def __init__(self, device='cuda', thr=CENSUS_THR, eps=CENSUS_EPS, per_pair=False):
-        super().__init__(thr, eps)
-        self.device = _device(device)
-        self.per_pair = bool(per_pair)
-        self.lib = hip.load()
-        self._tables, self._n = [], 0
+        CensusStats.__init__(self, thr, eps)
+        self._open(device, per_pair, [((2, CENSUS_CELLS), torch.int64)])
 
-    def _row(self):
-        i = self._n if self.per_pair else 0
-        if i >= 16 * len(self._tables):
-            self._tables.append(torch.zeros((16 if self.per_pair else 1, 2, CENSUS_CELLS), dtype=torch.int64, device=self.device))
-        return self._tables[i // 16][i % 16]
-
-    def add_pair(self, prev_frame, cur_frame, flow, mask=None, residual=None):
-        """count one pair into the open video (opened by the first pair); the arguments of `PhotoEvaluator.add_pair`"""
-        _census_accumulate(self.lib, cur_frame, prev_frame, flow, mask, self.thr, self.eps, self._row(), None, residual, self.device)
-        self._n += 1
-
-    def end_video(self, video_id=None):
-        """the one download (and synchronisation) of the open video; returns its entry"""
-        assert self._n, 'no video is open'
-        tables = (torch.cat(self._tables) if len(self._tables) > 1 else self._tables[0]).cpu().numpy()
-        n = self._n
-        self._tables, self._n = [], 0
-        return self.add_tables(video_id, tables[:n] if self.per_pair else tables[0], n)
-
-    def add_video(self, frames, flows, video_id=None, masks=None, residuals=None):
-        """as `PhotoEvaluator.add_video`"""
-        assert self._n == 0, 'a video opened by add_pair is not ended'
-        if len(flows) != len(frames) or any(x is not None and len(x) != len(frames) for x in (masks, residuals)):
-            raise ValueError('one flow (mask, residual) per frame, the first is not used: %d frames, %d flows' % (len(frames), len(flows)))
-        if len(frames) < 2:
-            return self.add_tables(video_id, np.zeros((2, CENSUS_CELLS), dtype=np.int64), 0)
-        for t in range(1, len(frames)):                  # no synchronisation between pairs
-            self.add_pair(frames[t - 1], frames[t], flows[t], mask=None if masks is None else masks[t], residual=None if residuals is None else residuals[t])
-        return self.end_video(video_id)
-
-    def result(self):
-        assert self._n == 0, 'a video opened by add_pair is not ended'
-        return super().result()
+    def _count_pair(self, cur, prev, flow, mask, residual, table):
+        _census_accumulate(self.lib, cur, prev, flow, mask, self.thr, self.eps, table, None, residual, self.device)
 
 
 def write_census_outputs(result, out_dir):
     """flow-census.txt and flow-census.json in `out_dir`"""
-    os.makedirs(out_dir, exist_ok=True)
-    with open(os.path.join(out_dir, 'flow-census.txt'), 'w') as f:
-        f.write(census_text(result))
-    with open(os.path.join(out_dir, 'flow-census.json'), 'w') as f:
-        json.dump(result, f, indent=1)
+    pairtables.write_result(result, out_dir, 'flow-census', census_text(result))
