@@ -934,6 +934,35 @@ int vps_png_deflate(const uint8_t* img, int H, int W, int channels, int64_t row_
 int vps_png_encode_bound_bpp(int H, int64_t rowbytes, int bpp, int64_t* out_capacity, int64_t* ws_bytes);
 int vps_png_deflate_bpp(const uint8_t* img, int H, int64_t rowbytes, int bpp, int64_t row_stride, uint8_t* out, int64_t out_capacity,
                         int64_t* out_nbytes, void* ws, int64_t ws_bytes, void* stream);
+/* The two calls above with the Huffman code as an argument, for dense images (flow files, colour images, error maps).
+ * huffman 0: the fixed code, byte for byte vps_png_deflate / vps_png_deflate_bpp. huffman 1: "dynamic", below. Any other value: -1007
+ * before any launch. Filter, segments, tokens, stream framing, bounds (vps_png_encode_bound*), workspace, pointers, alignments,
+ * out_nbytes and the other error codes are the same for both. The dynamic stream, per segment:
+ *   symbols  the segment's tokens as RFC 1951 literal/length symbols: a literal is its byte, a match its length symbol (3.2.5) with
+ *            its extra bits; every match has distance 1. count[s] = uses of symbol s in the segment, count[256] (end of block) = 1
+ *   lengths  LIMITED(count[0..285], 15). LIMITED(count, L) is package-merge: the n symbols with count > 0 are the leaves, in ascending
+ *            order of (count, symbol). List 1 = the leaves. List j (2..L) = the leaves merged by weight with the packages of list j-1
+ *            (item 2k + item 2k+1 for k = 0 .., an odd last item dropped); of a leaf and a package of equal weight the leaf comes
+ *            first; the list is cut to its first 2n-2 items. Start with k = 2n-2 at list L; at each list from L down to 1, if a of
+ *            its first k items are leaves, the a first leaves gain one bit and k becomes 2 (k - a). n = 1: that symbol gets length 1.
+ *            The lengths are optimal under the limit, so they cost what a Huffman tree costs wherever that tree is at most L deep
+ *   codes    canonical codes of the lengths (RFC 1951 3.2.2)
+ *   distance HDIST = 2: distance symbols 0 and 1 with length 1 each (a complete code); a match's distance is the single bit 0
+ *   header   BFINAL 0, BTYPE 10, HLIT = max(257, last symbol with a length + 1), HDIST, HCLEN. The HLIT + 2 lengths are ONE sequence,
+ *            coded per maximal run of equal values. R zeros: symbol 18 with min(R, 138) while R >= 11, then 17 if R >= 3, else R
+ *            times 0. R times v > 0: v once, then with R-1 left: 16 with min(left, 6) while left >= 3, then v for each one left.
+ *            cl_count[0..18] = uses of those symbols; their lengths = LIMITED(cl_count, 7), canonical codes; HCLEN = max(4, last
+ *            nonzero length in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15, + 1)
+ *   block    header, the tokens (code, extra bits, distance bit), end of block; D = its bits. F = the bits of the fixed block
+ *            (3 + tokens + 7)
+ *   choice   the segment is this block if F >= 512 and D < F, else the fixed block of vps_png_deflate, the same bytes. (A segment
+ *            under 512 bits is almost all runs, a label map's: a code of its own could save less than 64 bytes of 8192 there and is
+ *            not built. An all-zero segment, F = 439, stays fixed.) Either is
+ *            followed by the empty stored block, so a stream is never longer than the fixed one and the bounds do not change. */
+int vps_png_deflate_h(const uint8_t* img, int H, int W, int channels, int64_t row_stride, uint8_t* out, int64_t out_capacity,
+                      int64_t* out_nbytes, void* ws, int64_t ws_bytes, void* stream, int huffman);
+int vps_png_deflate_bpp_h(const uint8_t* img, int H, int64_t rowbytes, int bpp, int64_t row_stride, uint8_t* out, int64_t out_capacity,
+                          int64_t* out_nbytes, void* ws, int64_t ws_bytes, void* stream, int huffman);
 
 /* Optical-flow output (csrc/flow_vis_ops.hip; vps_amd/flowvis.py): the colour coding of the reference's flow_utils.py (vis_flow) on the
  * device. Both launch on `stream`, no sync, no hidden allocation. flow: DEVICE fp32 NHWC map of H x W pixels, pixel p at

@@ -39,6 +39,7 @@ def parse_args(argv=None):
     ap.add_argument('--occ-mask', default=None, help='directory of 8-bit PNGs, non-zero = occluded (Sintel occlusions)')
     ap.add_argument('--error-map', default=None, help='directory for the error images')
     ap.add_argument('--format', default='jpg', choices=('jpg', 'png'), help='format of the error images')
+    ap.add_argument('--png-huffman', default='fixed', choices=('fixed', 'dynamic'), help='--format png: the Huffman code of the device deflate stage; dynamic = a code per 8 KiB segment where that is shorter (dense images)')
     ap.add_argument('--out', default=None, help='directory for flow-eval.txt and flow-eval.json (default: --pred)')
     ap.add_argument('--device', default='cuda')
     args = ap.parse_args(argv)
@@ -133,7 +134,7 @@ def main(argv=None):
     ev = floweval.FlowEvaluator(args.device, per_pair=True)
     writer = None
     if args.error_map is not None:
-        writer = postprocess.DeviceJpegWriter(ev.device) if args.format == 'jpg' else postprocess.DevicePngWriter(ev.device)
+        writer = postprocess.DeviceJpegWriter(ev.device) if args.format == 'jpg' else postprocess.DevicePngWriter(ev.device, huffman=args.png_huffman)
     written = []
     try:
         for s, pred_path, gt_path, noc_path in pairs:

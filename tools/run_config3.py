@@ -51,6 +51,7 @@ def parse_args(argv=None):
     ap.add_argument('--strict', action='store_true', help='load_checkpoint(strict=True): missing / unexpected keys are fatal')
     ap.add_argument('--png-workers', type=int, default=6)
     ap.add_argument('--device-png', action='store_true', help='encode the result PNGs on the device (postprocess.DevicePngWriter) instead of PIL threads')
+    ap.add_argument('--png-huffman', default='fixed', choices=['fixed', 'dynamic'], help="--device-png, --flow-format png|kitti and PNG error maps: the Huffman code of the device deflate stage. fixed (default): the fixed code, right for label maps; dynamic: a code per 8 KiB segment where that is shorter, for dense images")
     ap.add_argument('--overlay', default=None, metavar='DIR', help='write DIR/<name>.jpg for every frame: the panoptic result blended over the frame (off by default; '
                     'keeps every decoded frame on the device until the maps are unified, 6 MB per frame at 1024x2048)')
     ap.add_argument('--overlay-quality', type=int, default=90)
@@ -250,7 +251,7 @@ def run(args, tmp):
     if args.flow:
         from vps_amd.flowvis import FlowWriter, flow_name
         model.keep_flow = True
-        flow_writer = FlowWriter(dev, fmt=args.flow_format, max_rad=args.flow_max_rad, entropy=args.jpeg_entropy)
+        flow_writer = FlowWriter(dev, fmt=args.flow_format, max_rad=args.flow_max_rad, entropy=args.jpeg_entropy, huffman=args.png_huffman)
     if with_tc or with_photo or with_census:
         model.keep_flow = True
         res['all_flows'] = []
@@ -305,7 +306,7 @@ def run(args, tmp):
         kw = dict(labeled_fid=args.dry_label_first, lambda_=5, nframes_per_video=len(names) // max(args.n_video, 1))
     if args.device_png:
         from vps_amd.postprocess import DevicePngWriter
-        kw['writer'] = DevicePngWriter(dev)
+        kw['writer'] = DevicePngWriter(dev, huffman=args.png_huffman)
     if args.tubes:
         from vps_amd.tubes import TubeCollector
         kw['tubes'] = TubeCollector(things_only=True, device=dev, id_last_stuff=unifier.id_last_stuff)

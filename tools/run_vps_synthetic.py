@@ -54,7 +54,7 @@ def uint8_frame(H, W, seed, shift):
     return synth.synth_frame(H, W, seed=seed, shift=shift, noise=2.0 if shift != (0, 0) else 0.0).astype(np.uint8)
 
 
-def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg_entropy='host', keep_flows=False, back_flows=False):
+def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg_entropy='host', keep_flows=False, back_flows=False, png_huffman='fixed'):
     """test_vpq.py:129-149 + single_gpu_test (:28-69) on `videos` synthetic clips -> pano_results with DEVICE maps.
     `flow` = (directory, format, max_rad): the FlowNet2 flow of EVERY frame as DIR/<name>.<format> (flowvis.FlowWriter).
     `keep_flows` (--tc): the device flow of every frame in res['all_flows'], 8 bytes per pixel and frame until `tc` has counted its pair.
@@ -80,7 +80,7 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg
     if flow:
         from vps_amd.flowvis import FlowWriter, flow_name
         model.keep_flow = True
-        flow_writer = FlowWriter(dev, fmt=flow[1], max_rad=flow[2], entropy=jpeg_entropy)
+        flow_writer = FlowWriter(dev, fmt=flow[1], max_rad=flow[2], entropy=jpeg_entropy, huffman=png_huffman)
     if keep_flows:
         model.keep_flow = True
         res['all_flows'] = []
@@ -117,7 +117,7 @@ def run_model(prec, videos, nframes, H, W, dev, separated=False, flow=None, jpeg
 
 
 def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_png=False, overlay=None, tubes=False, jpeg_entropy='host',
-                overlay_video=None, tc=None, flow_photo=None, flow_census=None):
+                overlay_video=None, tc=None, flow_photo=None, flow_census=None, png_huffman='fixed'):
     """test_vpq.py:178-198 with the device-side unifier / converter / asynchronous writer (`device_png`: the PNGs are filtered and
     deflated on the device too, postprocess.DevicePngWriter). `overlay` = (directory, quality, alpha): an overlay JPEG of EVERY frame,
     blended and transformed on the device (postprocess.write_overlays). `tubes`: tubes.json beside pred.json, the COCO run-length
@@ -145,7 +145,7 @@ def postprocess(res, out_dir, videos, dev, labeled_fid, lambda_, nper, device_pn
         tc['result'] = tc_score(pred_pans_2ch, res, keys, len(keys) // max(videos, 1), dev, out_dir, unifier.id_last_stuff, tc, jpeg_entropy)
     names = keys[(labeled_fid // lambda_)::lambda_]                               # names of the labelled frames (im_jsons['images'])
     cats = {c['id']: c for c in CATEGORIES}
-    writer = DevicePngWriter(dev) if device_png else None
+    writer = DevicePngWriter(dev, huffman=png_huffman) if device_png else None
     collector = None
     if tubes:
         from vps_amd.tubes import TubeCollector
@@ -318,6 +318,7 @@ def parse_args(argv=None):
     ap.add_argument('--separated', action='store_true', help='box classification layer of tests/golden/separated_fc_cls.npz (few, well-separated detections)')
     ap.add_argument('--out', default=os.path.join(ROOT, 'gpurun_out', 'vps_synth'))
     ap.add_argument('--device-png', action='store_true', help='encode the result PNGs on the device (postprocess.DevicePngWriter) instead of PIL threads')
+    ap.add_argument('--png-huffman', default='fixed', choices=['fixed', 'dynamic'], help="--device-png, --flow-format png|kitti and PNG error maps: the Huffman code of the device deflate stage. fixed (default): the fixed code, right for label maps; dynamic: a code per 8 KiB segment where that is shorter, for dense images")
     ap.add_argument('--overlay', default=None, metavar='DIR', help='write DIR/<name>.jpg for every frame: the panoptic result blended over the frame (off by default)')
     ap.add_argument('--overlay-quality', type=int, default=90)
     ap.add_argument('--overlay-alpha', type=int, default=128, help='weight of the colour map, 0..256')
@@ -393,16 +394,17 @@ def main(argv=None):
         flow_photo = dict(map_dir=args.flow_photo_map, thr=PHOTO_THR if args.tc_photometric is None else args.tc_photometric, alpha=args.overlay_alpha,
                           quality=args.overlay_quality)
     res, dt = run_model(args.prec, args.videos, args.frames, args.height, args.width, dev, args.separated, flow, args.jpeg_entropy,
-                        keep_flows=tc is not None or flow_photo is not None or flow_census is not None, back_flows=args.tc_occlusion)
+                        keep_flows=tc is not None or flow_photo is not None or flow_census is not None, back_flows=args.tc_occlusion,
+                        png_huffman=args.png_huffman)
     t0 = time.perf_counter()
     names, pans, pj = postprocess(res, os.path.join(args.out, 'pred'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png, overlay, args.tubes,
-                                  args.jpeg_entropy, overlay_video, tc, flow_photo, flow_census)
+                                  args.jpeg_entropy, overlay_video, tc, flow_photo, flow_census, png_huffman=args.png_huffman)
     dpost = time.perf_counter() - t0
     pred = (pans, pj)
     gt = pred
     if args.gt_prec:
         res2, _ = run_model(args.gt_prec, args.videos, args.frames, args.height, args.width, dev, args.separated)
-        _, pans2, pj2 = postprocess(res2, os.path.join(args.out, 'gt'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png)
+        _, pans2, pj2 = postprocess(res2, os.path.join(args.out, 'gt'), args.videos, dev, labeled_fid, lambda_, nper, args.device_png, png_huffman=args.png_huffman)
         gt = (pans2, pj2)
     t0 = time.perf_counter()
     score = vpq(gt, pred, args.videos, nper, dev)

@@ -180,6 +180,212 @@ __device__ __forceinline__ void emit_run(BitWriter& bw, uint32_t v, int R) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// the dynamic-Huffman instance of kernel 2 (vps_png_deflate_h, huffman = 1; the format is in include/vps_hip.h). Same tokens; the
+// workgroup then builds the segment's own code in LDS and writes an RFC 1951 dynamic block where that is shorter:
+//   histogram   286 literal/length counts (end-of-block 1) by LDS atomics, from the same walk over the run starts as pass A
+//   lengths     package-merge, limit 15 (pm_lengths below; limit 7 for the 19 code-length symbols through the same routine). Leaves =
+//               the symbols with a count, ascending by (count, symbol). List 1 = the leaves; list j = the leaves merged by weight with
+//               the packages of list j-1 (item 2k + item 2k+1, an odd last item dropped), a LEAF IN FRONT OF A PACKAGE OF EQUAL WEIGHT,
+//               cut to its first 2n-2 items. Top list: take k = 2n-2 items; a of them are leaves -> the a first leaves gain one bit,
+//               the list below gives 2 (k - a) items. Only "is item p of list j a leaf" is kept (one bit each), so the walk down
+//               is one masked popcount per level. Package-merge is optimal under the limit, so where the Huffman tree fits the cost is
+//               the Huffman cost. One symbol with a count gets length 1 (cannot happen here: a literal and end-of-block are always there)
+//   codes       canonical (RFC 1951 3.2.2), kept bit-reversed with the length in bits 16..
+//   header      by wave 0, five entries of the HLIT + 2 code lengths per lane: runs of equal lengths -> 16 / 17 / 18 by the greedy rule
+//               of cl_run, counted, coded with the limit-7 code, HCLEN trimmed in the RFC's order
+//   choice      dynamic only if the fixed block has >= PNG_DYN_MIN_FIXED bits and the dynamic one is strictly shorter; else pass B is
+//               the fixed instance's, bit for bit
+// LDS beside res32 / outw / msk and the wave sums (18.1 KiB): PngDyn, 10.6 KiB -> 28.7 KiB per workgroup.
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr int PNG_NSYM = 286;
+constexpr int PNG_NSYM_PAD = 288;
+constexpr int PNG_PM_ITEMS = 2 * PNG_NSYM - 2;                  // longest list of the package-merge
+constexpr int PNG_PM_WORDS = (PNG_PM_ITEMS + 31) / 32;
+constexpr uint32_t PNG_DYN_MIN_FIXED = 512;                     // bits of the fixed block below which a segment stays fixed
+__device__ const uint8_t PNG_CL_ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+
+struct PngDyn {
+    uint32_t hist[PNG_NSYM_PAD];              // literal/length counts
+    uint32_t leaf[PNG_NSYM_PAD];              // weights of the leaves in order
+    uint32_t rank[PNG_NSYM_PAD];              // place of a symbol among the leaves
+    uint32_t list[2][PNG_PM_ITEMS + 2];       // weights of list j-1 and list j
+    uint32_t lmask[15][PNG_PM_WORDS];         // bit p of level j: item p of list j is a leaf
+    uint32_t nleaf_taken[16];                 // a of each level
+    uint32_t code[PNG_NSYM_PAD];              // reversed code | length << 16
+    uint32_t clfreq[20], clcode[20];
+    uint8_t len[PNG_NSYM_PAD];
+    uint8_t cllen[20];
+    uint32_t wsum_d[PNG_WAVES];
+    uint32_t hdr_bits;
+};
+
+// freq[nsym] -> len[nsym], every length <= limit (nsym <= 286 <= 2^limit). Every thread of the workgroup calls it.
+__device__ void pm_lengths(const uint32_t* freq, int nsym, int limit, uint8_t* len, PngDyn& d) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    // order of the leaves: key = count << 9 | symbol
+    const int sa = tid, sb = tid + PNG_THREADS;
+    const uint32_t ca = sa < nsym ? freq[sa] : 0u, cb = sb < nsym ? freq[sb] : 0u;
+    const uint32_t ka = (ca << 9) | (uint32_t)sa, kb = (cb << 9) | (uint32_t)sb;
+    int n = 0, ra = 0, rb = 0;
+    for (int s = 0; s < nsym; ++s) {
+        const uint32_t c = freq[s];
+        const uint32_t k = c ? ((c << 9) | (uint32_t)s) : 0xFFFFFFFFu;
+        n += c != 0u; ra += k < ka; rb += k < kb;
+    }
+    if (ca) { d.rank[sa] = (uint32_t)ra; d.leaf[ra] = ca; }
+    if (cb) { d.rank[sb] = (uint32_t)rb; d.leaf[rb] = cb; }
+    for (int i = tid; i < 15 * PNG_PM_WORDS; i += PNG_THREADS) (&d.lmask[0][0])[i] = 0u;
+    __syncthreads();
+    if (n < 2) {
+        if (sa < nsym) len[sa] = ca ? 1 : 0;
+        if (sb < nsym) len[sb] = cb ? 1 : 0;
+        __syncthreads();
+        return;
+    }
+    const int cut = 2 * n - 2;
+    int mprev = 0;
+    for (int j = 0; j < limit; ++j) {
+        const uint32_t* prev = d.list[(j + 1) & 1];
+        uint32_t* cur = d.list[j & 1];
+        const int np = mprev >> 1;
+        for (int i = tid; i < n + np; i += PNG_THREADS) {
+            uint32_t w;
+            int pos;
+            if (i < n) {                                          // leaf i: in front of it, the packages lighter than it
+                w = d.leaf[i];
+                int lo = 0, hi = np;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (prev[2 * mid] + prev[2 * mid + 1] < w) lo = mid + 1; else hi = mid;
+                }
+                pos = i + lo;
+                if (pos < cut) atomicOr(&d.lmask[j][pos >> 5], 1u << (pos & 31));
+            } else {                                              // package k: in front of it, the leaves not heavier than it
+                const int k = i - n;
+                w = prev[2 * k] + prev[2 * k + 1];
+                int lo = 0, hi = n;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (d.leaf[mid] <= w) lo = mid + 1; else hi = mid;
+                }
+                pos = k + lo;
+            }
+            if (pos < cut) cur[pos] = w;
+        }
+        mprev = min(n + np, cut);
+        __syncthreads();
+    }
+    if (tid < 64) {                                               // the walk down, by wave 0
+        int k = cut;
+        for (int j = limit - 1; j >= 0; --j) {
+            uint32_t c = 0;
+            if (lane < PNG_PM_WORDS) {
+                const int lo = 32 * lane;
+                const uint32_t keep = k >= lo + 32 ? 0xFFFFFFFFu : (k > lo ? (1u << (k - lo)) - 1u : 0u);
+                c = (uint32_t)__popc(d.lmask[j][lane] & keep);
+            }
+            for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o);
+            if (lane == 0) d.nleaf_taken[j] = c;
+            k = 2 * (k - (int)c);
+        }
+    }
+    __syncthreads();
+    int la = 0, lb = 0;
+    for (int j = 0; j < limit; ++j) {
+        const uint32_t a = d.nleaf_taken[j];
+        la += a > (uint32_t)ra; lb += a > (uint32_t)rb;
+    }
+    if (sa < nsym) len[sa] = (uint8_t)(ca ? la : 0);
+    if (sb < nsym) len[sb] = (uint8_t)(cb ? lb : 0);
+    __syncthreads();
+}
+
+// canonical codes of len[nsym]: code = (sum over shorter symbols of 2^(own length - theirs)) + (symbols of the own length before it)
+__device__ void canonical_codes(const uint8_t* len, int nsym, uint32_t* code) {
+    for (int s = threadIdx.x; s < nsym; s += PNG_THREADS) {
+        const int l = len[s];
+        uint32_t c = 0;
+        if (l) {
+            for (int t = 0; t < nsym; ++t) {
+                const int lt = len[t];
+                if (lt && lt < l) c += 1u << (l - lt);
+                else if (lt == l && t < s) ++c;
+            }
+            c = (__brev(c) >> (32 - l)) | ((uint32_t)l << 16);
+        }
+        code[s] = c;
+    }
+    __syncthreads();
+}
+
+// length 3 .. 258 -> its symbol and the number of extra bits (RFC 1951 3.2.5)
+__device__ __forceinline__ int len_symbol(int L, int& e) {
+    const int l = L - 3;
+    e = 0;
+    if (L == 258) return 285;
+    if (l < 8) return 257 + l;
+    e = 29 - __clz(l);
+    return 261 + 4 * e + ((l >> e) & 3);
+}
+
+// the code-length tokens of one run of R equal lengths v: f(symbol, extra value, extra bits)
+template <class F>
+__device__ __forceinline__ void cl_run(int v, int R, F&& f) {
+    if (v == 0) {
+        while (R >= 11) { const int c = min(R, 138); f(18, c - 11, 7); R -= c; }
+        if (R >= 3) { f(17, R - 3, 3); R = 0; }
+        for (; R > 0; --R) f(0, 0, 0);
+    } else {
+        f(v, 0, 0); --R;
+        while (R >= 3) { const int c = min(R, 6); f(16, c - 3, 2); R -= c; }
+        for (; R > 0; --R) f(v, 0, 0);
+    }
+}
+
+// a lane's runs of the code-length sequence (entry i < hlit: len[i]; the two behind: 1, the distance code)
+template <class F>
+__device__ __forceinline__ void cl_walk(const uint8_t* len, int hlit, int lane, uint32_t m5, int nxt5, F&& f) {
+    for (uint32_t mm = m5; mm;) {
+        const int p = 5 * lane + __ffs((int)mm) - 1;
+        mm &= mm - 1;
+        const int q = mm ? 5 * lane + __ffs((int)mm) - 1 : nxt5;
+        cl_run(p < hlit ? (int)len[p] : 1, q - p, f);
+    }
+}
+
+__device__ __forceinline__ int dyn_run_bits(const uint32_t* code, uint32_t v, int R) {
+    const int lb = (int)(code[v] >> 16);
+    const int r = R - 1, nfull = r / 258, rem = r - nfull * 258;
+    int bits = lb + nfull * ((int)(code[285] >> 16) + 1);
+    if (rem >= 3) {
+        int e;
+        const int sym = len_symbol(rem, e);
+        bits += (int)(code[sym] >> 16) + e + 1;
+    } else {
+        bits += rem * lb;
+    }
+    return bits;
+}
+
+// a match is up to 15 + 5 + 1 bits: the code in one put, the extra bits and the distance code (one 0 bit) in a second
+__device__ __forceinline__ void dyn_emit_run(BitWriter& bw, const uint32_t* code, uint32_t v, int R) {
+    const uint32_t cv = code[v];
+    bw.put(cv & 0xFFFFu, (int)(cv >> 16));
+    const int r = R - 1, nfull = r / 258, rem = r - nfull * 258;
+    const uint32_t c285 = code[285];
+    for (int k = 0; k < nfull; ++k) bw.put(c285 & 0xFFFFu, (int)(c285 >> 16) + 1);
+    if (rem >= 3) {
+        int e;
+        const uint32_t c = code[len_symbol(rem, e)];
+        bw.put(c & 0xFFFFu, (int)(c >> 16));
+        bw.put((uint32_t)((rem - 3) & ((1 << e) - 1)), e + 1);
+    } else {
+        for (int k = 0; k < rem; ++k) bw.put(cv & 0xFFFFu, (int)(cv >> 16));
+    }
+}
+
+template <bool DYN>
 __global__ __launch_bounds__(PNG_THREADS)
 void png_encode_kernel(const uint8_t* __restrict__ img, int H, int rowlen, int C, int64_t stride, int64_t N,
                        const uint8_t* __restrict__ ftype, PngSegInfo* __restrict__ info, uint8_t* __restrict__ slots) {
@@ -189,6 +395,8 @@ void png_encode_kernel(const uint8_t* __restrict__ img, int H, int rowlen, int C
     __shared__ unsigned long long nzmask[PNG_WAVES];                         // which words of a wave hold a run start
     __shared__ uint32_t wsum[PNG_WAVES];
     __shared__ unsigned long long asum[2][PNG_WAVES];
+    __shared__ __attribute__((aligned(16))) uint32_t dyn_words[DYN ? (sizeof(PngDyn) + 3) / 4 : 1];
+    PngDyn& dy = *reinterpret_cast<PngDyn*>(dyn_words);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t base = (int64_t)blockIdx.x * PNG_SEG;
     const int n = (int)min((int64_t)PNG_SEG, N - base);
@@ -196,6 +404,10 @@ void png_encode_kernel(const uint8_t* __restrict__ img, int H, int rowlen, int C
     const uint32_t col0 = (uint32_t)(base - row0 * rowlen);
 
     for (int w = tid; w < PNG_OUT_WORDS; w += PNG_THREADS) outw[w] = 0;
+    if constexpr (DYN) {
+        for (int i = tid; i < PNG_NSYM_PAD; i += PNG_THREADS) dy.hist[i] = i == 256 ? 1u : 0u;
+        if (tid < 20) dy.clfreq[tid] = 0u;
+    }
     // stage 1: filter on the fly; four consecutive bytes of S per thread and step
     for (int w = tid; w < PNG_SEG / 4; w += PNG_THREADS) {
         const int i0 = 4 * w;
@@ -290,8 +502,119 @@ void png_encode_kernel(const uint8_t* __restrict__ img, int H, int rowlen, int C
         if (w < wave) before += wsum[w];
         tok_bits += wsum[w];
     }
+    bool use_dyn = false;
+    uint32_t dyn_total = 0;
+    if constexpr (DYN) {
+        if (3u + tok_bits + 7u >= PNG_DYN_MIN_FIXED) {                         // the same for the whole workgroup
+            // histogram: the walk of pass A
+            for (uint32_t mm = m; mm;) {
+                const int p = __ffs((int)mm) - 1;
+                mm &= mm - 1;
+                const int q = mm ? p0 + __ffs((int)mm) - 1 : nxt;
+                const uint32_t v = res8[p0 + p];
+                const int r = q - (p0 + p) - 1, nfull = r / 258, rem = r - nfull * 258;
+                atomicAdd(&dy.hist[v], 1u + (rem < 3 ? (uint32_t)rem : 0u));
+                if (nfull) atomicAdd(&dy.hist[285], (uint32_t)nfull);
+                if (rem >= 3) { int e; atomicAdd(&dy.hist[len_symbol(rem, e)], 1u); }
+            }
+            __syncthreads();
+            pm_lengths(dy.hist, PNG_NSYM, 15, dy.len, dy);
+            canonical_codes(dy.len, PNG_NSYM, dy.code);
+            // header, first half (wave 0): HLIT, the lane's run starts among its five entries, the counts of the code-length symbols
+            int hlit = 257, nxt5 = 0;
+            uint32_t m5 = 0;
+            if (wave == 0) {
+                const unsigned long long used = __ballot(lane < 29 && dy.len[257 + lane] != 0);
+                if (used) hlit = 257 + 64 - __clzll((long long)used);
+                const int T = hlit + 2;
+                for (int k = 0; k < 5; ++k) {
+                    const int i = 5 * lane + k;
+                    if (i >= T) break;
+                    const int cur = i < hlit ? (int)dy.len[i] : 1;
+                    const int prv = i == 0 ? -1 : (i - 1 < hlit ? (int)dy.len[i - 1] : 1);
+                    m5 |= (uint32_t)(cur != prv) << k;
+                }
+                const unsigned long long nz5 = __ballot(m5 != 0);
+                const unsigned long long later = lane == 63 ? 0ull : (nz5 >> (lane + 1)) << (lane + 1);
+                const int src = later ? __ffsll((long long)later) - 1 : lane;
+                const uint32_t ms = __shfl(m5, src);
+                nxt5 = later ? 5 * src + __ffs((int)ms) - 1 : T;
+                cl_walk(dy.len, hlit, lane, m5, nxt5, [&](int sym, int, int) { atomicAdd(&dy.clfreq[sym], 1u); });
+            }
+            __syncthreads();
+            pm_lengths(dy.clfreq, 19, 7, dy.cllen, dy);
+            canonical_codes(dy.cllen, 19, dy.clcode);
+            // header, second half: HCLEN, the bits of each lane's code-length tokens and where they start
+            int hclen = 4;
+            uint32_t hoff = 0;
+            if (wave == 0) {
+                const unsigned long long usedcl = __ballot(lane < 19 && dy.cllen[PNG_CL_ORDER[lane < 19 ? lane : 0]] != 0);
+                hclen = usedcl ? max(4, 64 - __clzll((long long)usedcl)) : 4;
+                uint32_t hb = 0;
+                cl_walk(dy.len, hlit, lane, m5, nxt5, [&](int sym, int, int eb) { hb += (dy.clcode[sym] >> 16) + (uint32_t)eb; });
+                uint32_t hincl = hb;
+                for (int d = 1; d < 64; d <<= 1) {
+                    const uint32_t o = __shfl_up(hincl, d);
+                    if (lane >= d) hincl += o;
+                }
+                hoff = 17u + 3u * (uint32_t)hclen + hincl - hb;
+                if (lane == 63) dy.hdr_bits = 17u + 3u * (uint32_t)hclen + hincl;
+            }
+            // pass A again with the segment's own code
+            uint32_t bits_d = 0;
+            for (uint32_t mm = m; mm;) {
+                const int p = __ffs((int)mm) - 1;
+                mm &= mm - 1;
+                const int q = mm ? p0 + __ffs((int)mm) - 1 : nxt;
+                bits_d += (uint32_t)dyn_run_bits(dy.code, res8[p0 + p], q - (p0 + p));
+            }
+            uint32_t incl_d = bits_d;
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t o = __shfl_up(incl_d, d);
+                if (lane >= d) incl_d += o;
+            }
+            if (lane == 63) dy.wsum_d[wave] = incl_d;
+            __syncthreads();
+            uint32_t before_d = 0, tok_d = 0;
+            for (int w = 0; w < PNG_WAVES; ++w) {
+                if (w < wave) before_d += dy.wsum_d[w];
+                tok_d += dy.wsum_d[w];
+            }
+            const uint32_t hdr_bits = dy.hdr_bits;
+            dyn_total = hdr_bits + tok_d + (dy.code[256] >> 16);
+            use_dyn = dyn_total < 3u + tok_bits + 7u;
+            if (use_dyn) {
+                // pass B with the segment's own code; the header's bits come first and are wave 0's
+                if (wave == 0) {
+                    BitWriter hw{outw, 0ull, (int)(hoff & 31u), (int)(hoff >> 5)};
+                    if (lane == 0) {
+                        hw = BitWriter{outw, 0ull, 0, 0};
+                        // BFINAL 0, BTYPE 10, HLIT - 257, HDIST - 1 = 1, HCLEN - 4
+                        hw.put(4u | ((uint32_t)(hlit - 257) << 3) | (1u << 8), 13);
+                        hw.put((uint32_t)(hclen - 4), 4);
+                        for (int i = 0; i < hclen; ++i) hw.put(dy.cllen[PNG_CL_ORDER[i]], 3);
+                    }
+                    cl_walk(dy.len, hlit, lane, m5, nxt5, [&](int sym, int ev, int eb) {
+                        const uint32_t c = dy.clcode[sym];
+                        hw.put((c & 0xFFFFu) | ((uint32_t)ev << (c >> 16)), (int)(c >> 16) + eb);
+                    });
+                    hw.flush();
+                }
+                const uint32_t off = hdr_bits + before_d + incl_d - bits_d;
+                BitWriter bw{outw, 0ull, (int)(off & 31u), (int)(off >> 5)};
+                for (uint32_t mm = m; mm;) {
+                    const int p = __ffs((int)mm) - 1;
+                    mm &= mm - 1;
+                    const int q = mm ? p0 + __ffs((int)mm) - 1 : nxt;
+                    dyn_emit_run(bw, dy.code, res8[p0 + p], q - (p0 + p));
+                }
+                if (tid == PNG_THREADS - 1) { const uint32_t c = dy.code[256]; bw.put(c & 0xFFFFu, (int)(c >> 16)); }   // end of block
+                bw.flush();
+            }
+        }
+    }
     // pass B: the same walk, emitting. 3 header bits (BFINAL 0, BTYPE 01) come first
-    {
+    if (!use_dyn) {
         const uint32_t off = 3u + before + incl - bits;
         BitWriter bw{outw, 0ull, (int)(off & 31u), (int)(off >> 5)};
         for (uint32_t mm = m; mm;) {
@@ -303,10 +626,10 @@ void png_encode_kernel(const uint8_t* __restrict__ img, int H, int rowlen, int C
         bw.flush();
     }
     // end of block (7 zero bits), empty stored block: 3 zero bits, zero bits to the byte boundary, 00 00 FF FF
-    const uint32_t total_bits = 3u + tok_bits + 7u + 3u;
+    const uint32_t total_bits = (use_dyn ? dyn_total : 3u + tok_bits + 7u) + 3u;
     const uint32_t nbytes = min((total_bits + 7u) / 8u + 4u, (uint32_t)PNG_SEG_MAX);           // (the bound holds by construction)
     if (tid == 0) {
-        atomicOr(&outw[0], 2u);
+        if (!use_dyn) atomicOr(&outw[0], 2u);
         for (uint32_t b = nbytes - 2; b < nbytes; ++b) atomicOr(&outw[b >> 2], 0xFFu << (8 * (b & 3u)));
         unsigned long long t1 = 0, t2 = 0;
         for (int w = 0; w < PNG_WAVES; ++w) { t1 += asum[0][w]; t2 += asum[1][w]; }
@@ -430,7 +753,7 @@ static int png_bound(int H, int64_t N, int64_t nseg, int64_t* out_capacity, int6
 }
 
 static int png_deflate_launch(const uint8_t* img, int H, int bpp, int64_t rowlen, int64_t N, int64_t nseg, int64_t row_stride, uint8_t* out,
-                              int64_t out_capacity, int64_t* out_nbytes, void* ws, int64_t ws_bytes, hipStream_t stream);
+                              int64_t out_capacity, int64_t* out_nbytes, void* ws, int64_t ws_bytes, int huffman, hipStream_t stream);
 
 }  // namespace
 
@@ -453,7 +776,17 @@ extern "C" int vps_png_deflate(const uint8_t* img, int H, int W, int channels, i
     int64_t rowlen, N, nseg;
     const int rc = png_geometry(H, W, channels, rowlen, N, nseg);
     if (rc) return rc;
-    return png_deflate_launch(img, H, channels, rowlen, N, nseg, row_stride, out, out_capacity, out_nbytes, ws, ws_bytes, (hipStream_t)stream_);
+    return png_deflate_launch(img, H, channels, rowlen, N, nseg, row_stride, out, out_capacity, out_nbytes, ws, ws_bytes, 0, (hipStream_t)stream_);
+}
+
+extern "C" int vps_png_deflate_h(const uint8_t* img, int H, int W, int channels, int64_t row_stride, uint8_t* out, int64_t out_capacity,
+                                 int64_t* out_nbytes, void* ws, int64_t ws_bytes, void* stream_, int huffman) {
+    if (huffman != 0 && huffman != 1) return VPS_EARG(7);
+    int64_t rowlen, N, nseg;
+    const int rc = png_geometry(H, W, channels, rowlen, N, nseg);
+    if (rc) return rc;
+    return png_deflate_launch(img, H, channels, rowlen, N, nseg, row_stride, out, out_capacity, out_nbytes, ws, ws_bytes, huffman,
+                              (hipStream_t)stream_);
 }
 
 extern "C" int vps_png_deflate_bpp(const uint8_t* img, int H, int64_t rowbytes, int bpp, int64_t row_stride, uint8_t* out, int64_t out_capacity,
@@ -461,13 +794,23 @@ extern "C" int vps_png_deflate_bpp(const uint8_t* img, int H, int64_t rowbytes, 
     int64_t rowlen, N, nseg;
     const int rc = png_geometry_bpp(H, rowbytes, bpp, rowlen, N, nseg);
     if (rc) return rc;
-    return png_deflate_launch(img, H, bpp, rowlen, N, nseg, row_stride, out, out_capacity, out_nbytes, ws, ws_bytes, (hipStream_t)stream_);
+    return png_deflate_launch(img, H, bpp, rowlen, N, nseg, row_stride, out, out_capacity, out_nbytes, ws, ws_bytes, 0, (hipStream_t)stream_);
+}
+
+extern "C" int vps_png_deflate_bpp_h(const uint8_t* img, int H, int64_t rowbytes, int bpp, int64_t row_stride, uint8_t* out,
+                                     int64_t out_capacity, int64_t* out_nbytes, void* ws, int64_t ws_bytes, void* stream_, int huffman) {
+    if (huffman != 0 && huffman != 1) return VPS_EARG(7);
+    int64_t rowlen, N, nseg;
+    const int rc = png_geometry_bpp(H, rowbytes, bpp, rowlen, N, nseg);
+    if (rc) return rc;
+    return png_deflate_launch(img, H, bpp, rowlen, N, nseg, row_stride, out, out_capacity, out_nbytes, ws, ws_bytes, huffman,
+                              (hipStream_t)stream_);
 }
 
 namespace {
 
 static int png_deflate_launch(const uint8_t* img, int H, int channels, int64_t rowlen, int64_t N, int64_t nseg, int64_t row_stride, uint8_t* out,
-                              int64_t out_capacity, int64_t* out_nbytes, void* ws, int64_t ws_bytes, hipStream_t stream) {
+                              int64_t out_capacity, int64_t* out_nbytes, void* ws, int64_t ws_bytes, int huffman, hipStream_t stream) {
     if (!img || !out || !out_nbytes || !ws) return VPS_EARG(3);
     if (row_stride < rowlen - 1 || out_capacity < 0) return VPS_EARG(4);
     if (((uintptr_t)ws & 15) || ((uintptr_t)out_nbytes & 7)) return VPS_EARG(5);
@@ -476,8 +819,12 @@ static int png_deflate_launch(const uint8_t* img, int H, int channels, int64_t r
     const int rowbytes = (int)(rowlen - 1);
     const int aligned = (((uintptr_t)img & 3) == 0 && (row_stride & 3) == 0) ? 1 : 0;
     hipLaunchKernelGGL(png_filter_kernel, dim3(H), dim3(PNG_THREADS), 0, stream, img, rowbytes, channels, row_stride, aligned, w.ftype);
-    hipLaunchKernelGGL(png_encode_kernel, dim3((unsigned)nseg), dim3(PNG_THREADS), 0, stream, img, H, (int)rowlen, channels, row_stride, N,
-                       (const uint8_t*)w.ftype, w.info, w.slots);
+    if (huffman)
+        hipLaunchKernelGGL(png_encode_kernel<true>, dim3((unsigned)nseg), dim3(PNG_THREADS), 0, stream, img, H, (int)rowlen, channels,
+                           row_stride, N, (const uint8_t*)w.ftype, w.info, w.slots);
+    else
+        hipLaunchKernelGGL(png_encode_kernel<false>, dim3((unsigned)nseg), dim3(PNG_THREADS), 0, stream, img, H, (int)rowlen, channels,
+                           row_stride, N, (const uint8_t*)w.ftype, w.info, w.slots);
     hipLaunchKernelGGL(png_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, (const PngSegInfo*)w.info, nseg, w.offset, w.ok, out,
                        out_capacity, out_nbytes);
     hipLaunchKernelGGL(png_gather_kernel, dim3((unsigned)nseg), dim3(PNG_THREADS), 0, stream, (const PngSegInfo*)w.info,

@@ -145,9 +145,11 @@ class FlowWriter:
     max_rad (jpg / png): None = each frame's own maximum (the reference); a float or device float64 scalar = one normaliser for all
     frames. Counters: `submitted`; after `close()`, which joins and re-raises a worker's exception: `written`, `bytes_written`."""
 
-    def __init__(self, device='cuda', workers=2, slots=4, fmt='jpg', quality=90, max_rad=None, entropy='host'):
+    def __init__(self, device='cuda', workers=2, slots=4, fmt='jpg', quality=90, max_rad=None, entropy='host', huffman='fixed'):
         if fmt not in FORMATS:
             raise ValueError('fmt is one of %s, got %r' % (FORMATS, fmt))
+        pp.png_huffman(huffman)
+        self.huffman = huffman                           # png / kitti: the Huffman code of the deflate stage ('fixed' | 'dynamic')
         self.device = torch.device(device)
         self.fmt = fmt
         self.max_rad = None if max_rad is None else max_rad_scalar(max_rad, self.device)
@@ -155,7 +157,7 @@ class FlowWriter:
         if fmt == 'jpg':
             self.images = pp.DeviceJpegWriter(self.device, workers=workers, slots=slots, quality=quality, entropy=entropy)
         elif fmt == 'png':
-            self.images = pp.DevicePngWriter(self.device, workers=workers, slots=slots)
+            self.images = pp.DevicePngWriter(self.device, workers=workers, slots=slots, huffman=huffman)
         else:
             import queue
             import threading
@@ -209,7 +211,7 @@ class FlowWriter:
         try:
             slot.fit(*kittiflow.png_encode_bound_bpp(H, 6 * W, 6))
             slot.image = kittiflow.kitti_flow_encode(flow)               # reads the flow on the current stream; alive until the worker is done
-            kittiflow.png_deflate_bpp(slot.image, 6, slot.out, slot.ws, slot.size)
+            kittiflow.png_deflate_bpp(slot.image, 6, slot.out, slot.ws, slot.size, huffman=self.huffman)
             slot.size_host.copy_(slot.size, non_blocking=True)
             slot.event.record()
         except BaseException:

@@ -42,7 +42,7 @@ SYMBOLS = [
     'vps_boundary_band', 'vps_boundary_band_ws', 'vps_boundary_tile',
     'vps_y4m_info', 'vps_y4m_frame_header', 'vps_y4m_write_header', 'vps_yuv_to_bgr', 'vps_bgr_to_yuv', 'vps_yuv_tile',
     'vps_png16_info', 'vps_png16_inflate', 'vps_kitti_flow_reconstruct_ws', 'vps_kitti_flow_reconstruct', 'vps_kitti_flow_encode',
-    'vps_png_encode_bound_bpp', 'vps_png_deflate_bpp',
+    'vps_png_encode_bound_bpp', 'vps_png_deflate_bpp', 'vps_png_deflate_h', 'vps_png_deflate_bpp_h',
 ]
 
 
@@ -251,6 +251,8 @@ def load():
     lib.vps_png_deflate.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]
     lib.vps_png_encode_bound_bpp.argtypes = [c_int, c_int64, c_int, POINTER(c_int64), POINTER(c_int64)]
     lib.vps_png_deflate_bpp.argtypes = [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.vps_png_deflate_h.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int]
+    lib.vps_png_deflate_bpp_h.argtypes = [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int]
     lib.vps_kitti_flow_reconstruct_ws.argtypes = [c_int, c_int, POINTER(c_int64)]
     lib.vps_kitti_flow_reconstruct.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]
     lib.vps_kitti_flow_encode.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]

@@ -106,9 +106,12 @@ def png_encode_bound_bpp(H, rowbytes, bpp):
     return cap.value, wsb.value
 
 
-def png_deflate_bpp(img, bpp, out=None, ws=None, size=None):
-    """filter + deflate a dense device uint8 [H, rowbytes] image whose pixels are bpp bytes (`vps_png_deflate_bpp`) on the current stream,
-    no sync -> (device uint8 buffer, device int64 [1] size); size -1 = `out` was too small"""
+def png_deflate_bpp(img, bpp, out=None, ws=None, size=None, huffman='fixed'):
+    """filter + deflate a dense device uint8 [H, rowbytes] image whose pixels are bpp bytes (`vps_png_deflate_bpp_h`) on the current
+    stream, no sync -> (device uint8 buffer, device int64 [1] size); size -1 = `out` was too small. huffman: 'fixed' (the bytes of
+    `vps_png_deflate_bpp`) or 'dynamic' (a segment in a Huffman code of its own where that is shorter), as `postprocess.png_deflate`"""
+    from .postprocess import png_huffman
+    huffman = png_huffman(huffman)
     assert img.is_cuda and img.dtype == torch.uint8 and img.dim() == 2 and img.is_contiguous()
     H, rowbytes = int(img.shape[0]), int(img.shape[1])
     if out is None or ws is None:
@@ -117,8 +120,8 @@ def png_deflate_bpp(img, bpp, out=None, ws=None, size=None):
         ws = torch.empty(wsb, dtype=torch.uint8, device=img.device) if ws is None else ws
     if size is None:
         size = torch.empty(1, dtype=torch.int64, device=img.device)
-    hip.check(hip.load().vps_png_deflate_bpp(hip.ptr(img), H, rowbytes, bpp, rowbytes, hip.ptr(out), out.numel(), hip.ptr(size), hip.ptr(ws),
-                                             ws.numel(), hip.stream_ptr()), 'vps_png_deflate_bpp')
+    hip.check(hip.load().vps_png_deflate_bpp_h(hip.ptr(img), H, rowbytes, bpp, rowbytes, hip.ptr(out), out.numel(), hip.ptr(size),
+                                               hip.ptr(ws), ws.numel(), hip.stream_ptr(), huffman), 'vps_png_deflate_bpp_h')
     return out, size
 
 
@@ -154,18 +157,18 @@ def read_kitti_flow(path_occ, path_noc=None, device='cuda'):
     return kitti_flow_reconstruct(scan, H, W, noc_valid)
 
 
-def kitti_flow_bytes(flow, valid=None):
+def kitti_flow_bytes(flow, valid=None, huffman='fixed'):
     """the complete file of a device flow (synchronises: one download of the stream and its size)"""
     t, _, _, H, W = flowvis._flow_view(flow)
-    out, size = png_deflate_bpp(kitti_flow_encode(flow, valid), 6)
+    out, size = png_deflate_bpp(kitti_flow_encode(flow, valid), 6, huffman=huffman)
     n = int(size.item())
     if n < 0:
         raise hip.VpsHipError('vps_png_deflate_bpp: the stream did not fit its worst-case bound')
     return png16_container(out[:n].cpu().numpy().tobytes(), H, W)
 
 
-def write_kitti_flow(flow, name, valid=None):
+def write_kitti_flow(flow, name, valid=None, huffman='fixed'):
     os.makedirs(os.path.dirname(name) or '.', exist_ok=True)
     with open(name, 'wb') as f:
-        f.write(kitti_flow_bytes(flow, valid))
+        f.write(kitti_flow_bytes(flow, valid, huffman))
     return name

@@ -228,10 +228,23 @@ def png_encode_bound(H, W, channels):
     return cap.value, wsb.value
 
 
-def png_deflate(t, out=None, ws=None, size=None):
-    """Filter + deflate a device uint8 [H,W,3] / [H,W] map on the device (`vps_png_deflate`: literals and distance-1 runs in the fixed
-    Huffman code) on the current stream, no sync. Returns (device uint8 buffer, device int64 [1] size): the zlib
-    stream is buffer[:size]; size -1 = `out` was too small. `out` / `ws` / `size`: caller-owned buffers (default: fresh worst-case ones)."""
+PNG_HUFFMAN = {'fixed': 0, 'dynamic': 1}
+
+
+def png_huffman(huffman):
+    """'fixed' | 'dynamic' -> the `huffman` argument of `vps_png_deflate_h`"""
+    if huffman not in PNG_HUFFMAN:
+        raise ValueError("huffman must be 'fixed' or 'dynamic', got %r" % (huffman,))
+    return PNG_HUFFMAN[huffman]
+
+
+def png_deflate(t, out=None, ws=None, size=None, huffman='fixed'):
+    """Filter + deflate a device uint8 [H,W,3] / [H,W] map on the device (`vps_png_deflate_h`: literals and distance-1 runs, DESIGN.md 6
+    row 2b) on the current stream, no sync. huffman 'fixed' = every segment in the fixed Huffman code (the bytes of `vps_png_deflate`);
+    'dynamic' = a segment in a code of its own where that is shorter (dense images). Returns (device uint8 buffer, device int64 [1]
+    size): the zlib stream is buffer[:size]; size -1 = `out` was too small. `out` / `ws` / `size`: caller-owned buffers (default: fresh
+    worst-case ones; the bound is the same for both codes)."""
+    huffman = png_huffman(huffman)
     t, H, W, C, stride = _png_view(t)
     if out is None or ws is None:
         cap, wsb = png_encode_bound(H, W, C)
@@ -239,8 +252,8 @@ def png_deflate(t, out=None, ws=None, size=None):
         ws = torch.empty(wsb, dtype=torch.uint8, device=t.device) if ws is None else ws
     if size is None:
         size = torch.empty(1, dtype=torch.int64, device=t.device)
-    hip.check(hip.load().vps_png_deflate(hip.ptr(t), H, W, C, stride, hip.ptr(out), out.numel(), hip.ptr(size), hip.ptr(ws), ws.numel(),
-                                         hip.stream_ptr()), 'vps_png_deflate')
+    hip.check(hip.load().vps_png_deflate_h(hip.ptr(t), H, W, C, stride, hip.ptr(out), out.numel(), hip.ptr(size), hip.ptr(ws), ws.numel(),
+                                           hip.stream_ptr(), huffman), 'vps_png_deflate_h')
     return out, size
 
 
@@ -293,10 +306,12 @@ class DevicePngWriter:
     like `AsyncPngWriter`. Counters: `device_encoded`, `fallback_encoded`. `close()` joins and re-raises a worker's exception."""
     accepts_device = True
 
-    def __init__(self, device='cuda', workers=2, slots=8):
+    def __init__(self, device='cuda', workers=2, slots=8, huffman='fixed'):
         import queue
         import threading
         from concurrent.futures import ThreadPoolExecutor
+        png_huffman(huffman)
+        self.huffman = huffman       # 'fixed' | 'dynamic': the Huffman code of `png_deflate`
         self.device = torch.device(device)
         self.pool = ThreadPoolExecutor(max_workers=workers)
         self.futures = []
@@ -357,7 +372,7 @@ class DevicePngWriter:
         try:
             slot.fit(*png_encode_bound(H, W, C))
             slot.image = t                               # alive until the worker is done with it
-            png_deflate(t, slot.out, slot.ws, slot.size)
+            png_deflate(t, slot.out, slot.ws, slot.size, huffman=self.huffman)
             slot.size_host.copy_(slot.size, non_blocking=True)
             slot.event.record()
         except BaseException:
